@@ -4,8 +4,14 @@
 Headline (``value``): mel-frames/s of Tacotron-2 encoder + decoder loop + Postnet inference on
 configs[1] ("decoder+Postnet inference, batch=32x200-char synthetic, 1xMI355X"): one step = one full
 synthesis of a 32-utterance batch (200 chars + EOS, T_out = 1000 decoder frames, random-init fp32
-weights of the fork-default architecture, D_mem = 1024).  The ``wavenet`` object carries
-configs[2] (24-layer R=64 MoL WaveNet, batch 1, 22.05 kHz): audio-samples/s.
+weights of the fork-default architecture, D_mem = 1024).  A plain run sets up, warms up, times
+``--steps`` such steps and prints the headline line (``ms_per_step`` = one timed step);
+``--dump-outputs DIR`` also writes the last timed step's outputs as .npy files.
+
+``--full`` adds every other leg to the same line: the decoder roofline against the measured HBM copy
+peak, the ``wavenet`` object (configs[2]: 24-layer R=64 MoL WaveNet, batch 1, 22.05 kHz,
+audio-samples/s; batched and reference-width runs), ``e2e`` (configs[3]), ``griffin_lim``, ``train``
+(configs[4]), ``variants`` and the CPU baselines; each leg has its ``--no-*`` switch.
 
 Multi-GPU (``--gpus N``; bench.py starts the N ranks itself under torch.distributed.run when it is
 not already one of them, and refuses a WORLD_SIZE that disagrees with --gpus): one rank per GPU,
@@ -40,6 +46,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every other leg (roofline with the measured HBM "
+                        "copy peak, WaveNet, end-to-end, Griffin-Lim, training step, model variants, CPU "
+                        "baselines; each has its --no-* switch); a plain run times the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to DIR/<name>.npy "
+                        "(float32; rank 0's batch): mel_outputs [B, frames, num_mels], stop_tokens "
+                        "[B, frames], decoded_frames [1]")
     p.add_argument("--batch", type=int, default=32)
     p.add_argument("--chars", type=int, default=200)
     p.add_argument("--ref-frames", type=int, default=400)
@@ -564,6 +578,18 @@ def bench_variants(a, local):
     return out
 
 
+def dump_outputs(path, mel_d, stop_d, B, frames, num_mels):
+    """--dump-outputs: the arrays tt2_synthesize_dev left for its caller in the last timed step, as
+    float32 .npy files.  mel_d is packed [B][frames][num_mels] (include/tt2.h), stop_d keeps its
+    row stride of max_iters * outputs_per_step."""
+    os.makedirs(path, exist_ok=True)
+    mel = mel_d.reshape(-1)[:B * frames * num_mels].reshape(B, frames, num_mels).cpu().numpy()
+    stop = stop_d[:, :frames].cpu().numpy()
+    np.save(os.path.join(path, "mel_outputs.npy"), np.ascontiguousarray(mel, np.float32))
+    np.save(os.path.join(path, "stop_tokens.npy"), np.ascontiguousarray(stop, np.float32))
+    np.save(os.path.join(path, "decoded_frames.npy"), np.asarray([frames], np.float32))
+
+
 def _profiled():
     """Running under rocprofv3 (its tool library is preloaded), or TT2_EXIT_GUARD=1."""
     return ("rocprofiler" in os.environ.get("LD_PRELOAD", "")
@@ -574,6 +600,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))  # the N ranks run as children; their rank 0 prints the line
     world, rank, local = world_from_env(a)
@@ -611,7 +639,8 @@ def main():
     # measured HBM copy bandwidth of this GPU (the spec peak confirmed on the box),
     # reported beside the spec-priced roofline fractions
     hbm_meas = ctypes.c_double(0.0)
-    _lib.check(lib.tt2_hbm_copy_gbps(local, ctypes.c_longlong(1 << 30), 5, ctypes.byref(hbm_meas)))
+    if a.full:
+        _lib.check(lib.tt2_hbm_copy_gbps(local, ctypes.c_longlong(1 << 30), 5, ctypes.byref(hbm_meas)))
     hbm_meas = round(hbm_meas.value, 1)
 
     def meas(achieved):  # the measured-peak companion fields of an HBM roofline
@@ -658,6 +687,34 @@ def main():
     _lib.check(lib.tt2_last_timings(eng.h, ms3))
     phases = dict(encode_ms=round(ms3[0], 3), decode_ms=round(ms3[1], 3), postnet_ms=round(ms3[2], 3),
                   decode_us_per_step=round(1000.0 * ms3[1] / max(n_steps.value, 1), 3))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mel_d, stop_d, B, n_steps.value * hp.outputs_per_step, hp.num_mels)
+
+    def headline(**legs):
+        return dict(metric=METRIC, value=round(value, 1), unit="mel-frames/s", n_gpus=world,
+                    steps=a.steps, warmup=a.warmup, ms_per_step=round(1000.0 * el / a.steps, 3),
+                    higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32",
+                    dtype_note=("fp32 storage and accumulation; the decoder / encoder / WaveNet products run as "
+                                "split fp16x3 MFMA (hi/lo fp16 halves, ~2^-22 relative; DESIGN 5.1)"),
+                    data="synthetic (seeded ids/ref mels, random-init weights)",
+                    config=dict(workload="configs[1]: Tacotron-2 encoder+decoder+Postnet inference, "
+                                         "batch=32x200-char synthetic, T_out=1000, 1 batch per GPU",
+                                global_batch=B * world, chars=a.chars, t_out=a.t_out,
+                                decoded_steps=n_steps.value, ref_frames=a.ref_frames,
+                                parallelism="utterance-batch sharding x{}".format(world)),
+                    phases=phases, full=bool(a.full), **legs)
+
+    def finish():
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        if guard:
+            _lib.load_library().tt2_exit_guard(0, 0)  # success: the guard's _exit status
+
+    if not a.full:  # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(headline()))
+        return finish()
 
     # --- dominant kernel roofline ---
     persist, pd_ms = eng.decoder_path()
@@ -692,7 +749,7 @@ def main():
                       "persist_stage_us_min": [round(float(v), 2) for v in np.nanmin(rel, 0)],
                       "persist_stage_us_max": [round(float(v), 2) for v in np.nanmax(rel, 0)],
                       "persist_stage_argmax_wg": [int(v) for v in np.nanargmax(np.nan_to_num(rel, nan=-1), 0)]}
-            np.save(os.path.join(ROOT, "gpurun_out", "pd_stamps.npy"), arr)
+            np.save(os.environ.get("TT2_STAMP_OUT", "pd_stamps.npy"), arr)
     else:
         us7 = (ctypes.c_float * 10)()
         _lib.check(lib.tt2_profile_decoder_kernels(eng.h, a.profile_iters, us7))
@@ -888,26 +945,9 @@ def main():
                            "thread per utterance".format(cores, nb_))
 
     if rank == 0:
-        out = dict(metric=METRIC, value=round(value, 1), unit="mel-frames/s", n_gpus=world,
-                   steps=a.steps, warmup=a.warmup, ms_per_step=round(1000.0 * el / a.steps, 3),
-                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32",
-                   dtype_note=("fp32 storage and accumulation; the decoder / encoder / WaveNet products run as "
-                               "split fp16x3 MFMA (hi/lo fp16 halves, ~2^-22 relative; DESIGN 5.1)"),
-                   data="synthetic (seeded ids/ref mels, random-init weights)",
-                   config=dict(workload="configs[1]: Tacotron-2 encoder+decoder+Postnet inference, "
-                                        "batch=32x200-char synthetic, T_out=1000, 1 batch per GPU",
-                               global_batch=B * world, chars=a.chars, t_out=a.t_out,
-                               decoded_steps=n_steps.value, ref_frames=a.ref_frames,
-                               parallelism="utterance-batch sharding x{}".format(world)),
-                   phases=phases, roofline=roofline, cpu_baseline=cpu, wavenet=wn, e2e=e2e,
-                   griffin_lim=glr, train=trn, variants=variants,
-                   diag_stamps=stamps)
-        print(json.dumps(out))
-    eng.close()
-    if world > 1:
-        dist.destroy_process_group()
-    if guard:
-        _lib.load_library().tt2_exit_guard(0, 0)  # success: the guard's _exit status
+        print(json.dumps(headline(roofline=roofline, cpu_baseline=cpu, wavenet=wn, e2e=e2e, griffin_lim=glr,
+                                  train=trn, variants=variants, diag_stamps=stamps)))
+    finish()
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""Summarise gpurun_out/pd_stamps.npy (TT2_STAMP_STEP stage stamps of k_decode_persist, 256 x 32
+"""Summarise pd_stamps.npy (TT2_STAMP_STEP stage stamps of k_decode_persist, 256 x 32
 s_memrealtime values at 100 MHz) per stage: median / max over work-groups, proj vs other."""
 import sys
 
@@ -9,7 +9,7 @@ NAMES = {0: "start", 1: "A pre taken", 18: "A mfma", 19: "A red", 2: "H1 pub", 3
          21: "softmax", 10: "CTX pub", 11: "CTX wait(proj)", 12: "PP put", 13: "RG2 tail0", 20: "PP take",
          14: "prenet", 15: "end"}
 ORDER = [0, 1, 18, 19, 2, 3, 4, 16, 17, 5, 6, 7, 8, 9, 21, 10, 11, 12, 13, 20, 14, 15]
-s = np.load(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pd_stamps.npy").astype(np.int64)
+s = np.load(sys.argv[1] if len(sys.argv) > 1 else "pd_stamps.npy").astype(np.int64)
 r = (s - s[:, 0].min()) * 0.01
 g = np.arange(256)
 for i in ORDER:

@@ -1,4 +1,7 @@
 """Shared test helpers: configs, seeded synthetic inputs, oracle hparams."""
+import os
+import shutil
+
 import numpy as np  # noqa: F401
 
 from oracle.hp import oracle_hp, wavenet_oracle_hp  # noqa: F401
@@ -29,6 +32,38 @@ def small_wavenet_hparams(layers=6, stacks=2):
     return hp
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def refnet_emt_fixture():
+    """The 42 trained refnet_emt tensors of the reference's ckpt-5200 (made by
+    tests/golden/make_ckpt_fixture.py; two .npz halves, each under the size limit of a committed
+    file)."""
+    W = {}
+    for half in "ab":
+        with np.load(os.path.join(GOLDEN, "refnet_emt_ckpt5200_{}.npz".format(half))) as z:
+            W.update({k: z[k] for k in z.files})
+    return W
+
+
+def refnet_checkpoint_dir(scope, dst):
+    """The reference's trained reference-encoder checkpoint directory of `scope` ('emt' | 'spk'),
+    put together under `dst` from tests/golden/refnet_ckpt/<scope>: the `checkpoint` and `.index`
+    files as they are, the `.data` shard joined from its `.partN` pieces."""
+    src = os.path.join(GOLDEN, "refnet_ckpt", scope)
+    os.makedirs(dst, exist_ok=True)
+    shards = {}
+    for f in sorted(os.listdir(src)):
+        if ".part" in f:
+            shards.setdefault(f[:f.rindex(".part")], []).append(f)
+        else:
+            shutil.copy(os.path.join(src, f), os.path.join(dst, f))
+    for shard, parts in shards.items():
+        with open(os.path.join(dst, shard), "wb") as out:
+            for p in sorted(parts, key=lambda p: int(p[p.rindex(".part") + 5:])):
+                with open(os.path.join(src, p), "rb") as f:
+                    out.write(f.read())
+    return dst
 
 
 # configs[3] at the fork-default Tacotron widths (VERDICT r04 item 1): three ~135-200 character

@@ -1,26 +1,18 @@
 """TF tensor-bundle checkpoint reader (tt2.ckpt), CPU only.
 
 * a synthetic bundle written by a minimal SSTable/protobuf writer below round-trips exactly;
-* when /root/reference is present (build container only): both trained reference-encoder
-  checkpoints the reference restores into its refnet scopes (tacotron/train.py:284-285,
-  330-338) parse, map 1:1 onto this build's variable names/shapes, and the committed fixture
-  tests/golden/refnet_emt_ckpt5200.npz equals the checkpoint bit for bit;
+* both trained reference-encoder checkpoints the reference restores into its refnet scopes
+  (tacotron/train.py:284-285, 330-338; committed under tests/golden/refnet_ckpt/, the data shard
+  in pieces) parse, map 1:1 onto this build's variable names/shapes, and the committed fixture
+  tests/golden/refnet_emt_ckpt5200_{a,b}.npz equals the checkpoint bit for bit;
 * the oracle reference encoder runs on the trained weights (finite, tanh-bounded output).
 """
-import os
 import struct
 
 import numpy as np
 import pytest
 
-from _common import full_hparams, oracle_hp
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-REF_CKPTS = {
-    "refnet_emt": "/root/reference/code/spk_disc/pretrained_model_emt_disc",
-    "refnet_spk": "/root/reference/code/spk_disc/pretrained_model_spk_disc",
-}
-FIXTURE = os.path.join(HERE, "golden", "refnet_emt_ckpt5200.npz")
+from _common import full_hparams, oracle_hp, refnet_checkpoint_dir, refnet_emt_fixture
 
 
 # ---- a minimal tensor-bundle writer (test-only) ----
@@ -122,11 +114,12 @@ def test_shim_load_checkpoint_scopes(tmp_path):
         model.load_checkpoint(str(tmp_path / "bad.ckpt-1"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CKPTS["refnet_emt"]), reason="reference checkout not present")
-def test_reference_refnet_checkpoints_map_onto_model():
+def test_reference_refnet_checkpoints_map_onto_model(tmp_path):
     from tt2 import ckpt
     from tt2.weights import init_tacotron_weights
     W = init_tacotron_weights(full_hparams())
+    REF_CKPTS = {"refnet_emt": refnet_checkpoint_dir("emt", str(tmp_path / "emt")),
+                 "refnet_spk": refnet_checkpoint_dir("spk", str(tmp_path / "spk"))}
     for scope, d in REF_CKPTS.items():
         prefix = ckpt.latest_checkpoint(d)
         vals = ckpt.read_checkpoint(prefix)
@@ -136,18 +129,17 @@ def test_reference_refnet_checkpoints_map_onto_model():
             assert k in W and W[k].shape == v.shape, k
             assert np.isfinite(v).all()
     emt = ckpt.read_checkpoint(ckpt.latest_checkpoint(REF_CKPTS["refnet_emt"]))
-    with np.load(FIXTURE) as z:
-        assert set(z.files) == {k for k in emt if "/refnet_emt/" in k}
-        for k in z.files:
-            np.testing.assert_array_equal(z[k], emt[k])
+    z = refnet_emt_fixture()
+    assert set(z) == {k for k in emt if "/refnet_emt/" in k}
+    for k in z:
+        np.testing.assert_array_equal(z[k], emt[k])
 
 
 def test_oracle_refnet_on_trained_weights():
     """The trained refnet_emt (fixture) through the oracle's ReferenceEncoder: finite output in
     (-1, 1) (dense tanh, modules.py:63) that differs between two different reference mels."""
     from oracle import tacotron_ref as TR
-    with np.load(FIXTURE) as z:
-        W = {k: z[k] for k in z.files}
+    W = refnet_emt_fixture()
     rng = np.random.default_rng(3)
     mel = rng.uniform(-4, 4, (2, 96, 80)).astype(np.float32)
     out = TR.reference_encoder(mel, W, "refnet_emt/")

@@ -234,16 +234,14 @@ def test_persistent_full_batch_free_run(full_setup):
 
 def test_trained_refnet_weights_persistent(full_setup):
     """The reference's own trained emotion reference encoder (refnet_emt, ckpt-5200, restored
-    the way tacotron/train.py:284 does; committed as tests/golden/refnet_emt_ckpt5200.npz) in
+    the way tacotron/train.py:284 does; committed as tests/golden/refnet_emt_ckpt5200_{a,b}.npz) in
     place of the random refnet_emt weights: encoder + style path + persistent decoder vs oracle."""
-    import os
+    from _common import refnet_emt_fixture
     hp, W = full_setup
-    fx = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refnet_emt_ckpt5200.npz")
     W2 = dict(W)
-    with np.load(fx) as z:
-        for k in z.files:
-            assert W2[k].shape == z[k].shape, k
-            W2[k] = z[k]
+    for k, v in refnet_emt_fixture().items():
+        assert W2[k].shape == v.shape, k
+        W2[k] = v
     _decode_compare(hp, W2, B=32, T=121, T_ref=96, n=30, seed=31)
 
 
