@@ -37,6 +37,23 @@ void set_last_error(const std::string& msg);
     if (!(cond)) throw ::tt2::Error(status, msg);                                          \
   } while (0)
 
+// ------------------------------------------------------------------------------------------
+// Environment switches (DESIGN.md "Environment switches" lists every one).  One parse rule: unset
+// or empty -> the default; otherwise strtol (base 0); a value that does not parse -> the default.
+// ------------------------------------------------------------------------------------------
+inline int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  if (!e || !e[0]) return dflt;
+  char* end = nullptr;
+  const long v = std::strtol(e, &end, 0);
+  return end == e ? dflt : (int)v;
+}
+inline bool env_on(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }  // 0 off, else on
+inline std::string env_str(const char* name, const char* dflt) {  // file names and mode words
+  const char* e = std::getenv(name);
+  return e && e[0] ? e : dflt;
+}
+
 std::string redzone_check_all(const char* phase);  // TT2_REDZONE: every live buffer, unnamed
 
 // Redzones (TT2_REDZONE=1, debug only): every DevBuf gets kRedzone extra bytes past its end filled
@@ -44,10 +61,7 @@ std::string redzone_check_all(const char* phase);  // TT2_REDZONE: every live bu
 // first buffer whose redzone a kernel wrote -- the buffer that overflowed, whatever the address
 // layout of the process puts behind it.
 inline bool redzone_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("TT2_REDZONE");
-    return e && e[0] && e[0] != '0';
-  }();
+  static const bool on = env_on("TT2_REDZONE", false);
   return on;
 }
 template <class F>
@@ -75,10 +89,8 @@ tt2_status guard(F&& f) {
 // that a max / compare would swallow as NaN still changes the result).
 inline int poison_alloc() {
   static const int fill = [] {
-    const char* e = std::getenv("TT2_POISON_ALLOC");
-    if (!e || !e[0] || (e[0] == '0' && !e[1])) return -1;
-    const long v = std::strtol(e, nullptr, 0);
-    return v == 1 ? 0xFF : (int)(v & 0xFF);
+    const int v = env_int("TT2_POISON_ALLOC", 0);
+    return v == 0 ? -1 : v == 1 ? 0xFF : v & 0xFF;
   }();
   return fill;
 }
@@ -111,6 +123,9 @@ struct DevBuf {
       bytes = n;
       if (rz) redzone_register(this, true);
     }
+  }
+  void reserve(size_t n) {  // grow only: the contents do not survive a growth
+    if (bytes < n) alloc(n);
   }
   void free() {
     if (p) {
@@ -304,7 +319,7 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // makes the runtime refuse a grid that cannot be co-resident.  TT2_COOP=0 launches the same grid
 // with hipLaunchKernel (after the same occupancy checks): a diagnostic switch for profiler runs.
 inline hipError_t launch_persistent(const void* f, dim3 grid, dim3 block, void** args, size_t shm, hipStream_t s) {
-  static const bool coop = !(getenv("TT2_COOP") && atoi(getenv("TT2_COOP")) == 0);
+  static const bool coop = env_on("TT2_COOP", true);
   return coop ? hipLaunchCooperativeKernel(f, grid, block, args, (unsigned)shm, s)
               : hipLaunchKernel(f, grid, block, args, shm, s);
 }

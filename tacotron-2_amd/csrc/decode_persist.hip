@@ -1244,10 +1244,7 @@ void pd_launch(const PdArgs& a, hipStream_t s, bool emt, int tm) {
   TT2_CHECK(a.T_in >= 1 && a.T_in <= tm, TT2_ERR_INVALID_ARG, "persistent decoder: T_in outside the kernel's range");
   PdArgs arg = a;
   void* params[] = {&arg};
-  static const bool floor_env = [] {  // diagnostic: the arithmetic-free floor instance (see FL)
-    const char* e = std::getenv("TT2_PD_FLOOR");
-    return e && e[0] == '1';
-  }();
+  static const bool floor_env = env_on("TT2_PD_FLOOR", false);  // diagnostic: the arithmetic-free floor instance (see FL)
   const void* k = emt ? reinterpret_cast<const void*>(k_decode_persist<true, PD_TMAX, false>)
                   : tm != PD_TMAX ? reinterpret_cast<const void*>(k_decode_persist<false, PD_TMAX_LONG, false>)
                   : floor_env     ? reinterpret_cast<const void*>(k_decode_persist<false, PD_TMAX, true>)

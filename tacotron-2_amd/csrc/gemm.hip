@@ -685,10 +685,7 @@ static bool rd_plan(const GemmArgs& a, int& ks, int& kslice) {
   const int nt = (a.N + RD_BN - 1) / RD_BN;
   // ~one work-group per CU (TT2_RD_TARGET work-groups), but >= 4 k-steps per slice: a small
   // product is not worth its partials
-  static const int target = [] {
-    const char* e = std::getenv("TT2_RD_TARGET");
-    return e ? std::max(1, std::atoi(e)) : 256;
-  }();
+  static const int target = std::max(1, env_int("TT2_RD_TARGET", 256));
   ks = std::max(1, std::min(a.K / 128, target / std::max(nt, 1)));
   for (;;) {
     kslice = ((a.K + ks - 1) / ks + 31) / 32 * 32;
@@ -1241,14 +1238,13 @@ void conv_x3(const ConvX3Args& a, hipStream_t s) {
   TT2_CHECK((a.Oh != nullptr) != (a.Cout != nullptr), TT2_ERR_INVALID_ARG, "conv_x3: exactly one output");
   TT2_CHECK(!a.Oh || (a.Ol && a.N % CX_BN == 0 && a16(a.Oh) && a16(a.Ol)), TT2_ERR_INVALID_ARG,
             "conv_x3: planes output needs N % 128 == 0 and aligned planes");
-  const char* ew = std::getenv("TT2_CX_WIDE");  // 0: the 128 x 128 register-staged kernel for every layer
-  const bool wide = !ew || std::atoi(ew) != 0;
+  const bool wide = env_on("TT2_CX_WIDE", true);  // 0: the 128 x 128 register-staged kernel for every layer
   if (a.ks > 1) {  // split K over blockIdx.y + one combine launch
     const long mrows = (long)a.B * (a.T + 2 * CX_P);
     TT2_CHECK(a.part && a.N % 4 == 0 && (long)a.ks * mrows * a.N <= a.part_floats && a.ks <= a.kw * a.Cp / X3_BK,
               TT2_ERR_INVALID_ARG, "conv_x3: split-K needs part >= ks x rows x N floats, N % 4 == 0");
-    const char* ewk = std::getenv("TT2_CX_WIDE_SPLIT");  // 0: the 128 x 128 kernel for the K-split layers
-    if (a.N % CXW_BN == 0 && (!ewk || std::atoi(ewk) != 0)) {
+    // TT2_CX_WIDE_SPLIT=0: the 128 x 128 kernel for the K-split layers
+    if (a.N % CXW_BN == 0 && env_on("TT2_CX_WIDE_SPLIT", true)) {
       const int n_mt = cdiv(a.B * (a.T + 2 * CX_P), CXW_BM), n_nt = a.N / CXW_BN;
       hipLaunchKernelGGL((conv_x3w_kernel<ACT_NONE, true>), dim3((unsigned)(cdiv(n_mt, 8) * 8 * n_nt), (unsigned)a.ks),
                          dim3(512), 0, s, a, n_mt, n_nt);
@@ -1569,10 +1565,9 @@ int gemm_impl(const GemmArgs& a, hipStream_t s) {
     TT2_CHECK(!a.Bt16 || (al16(a.Bt16) && a.ldbt % 8 == 0 && (a.split16 == 2 || (a.Bt16lo && al16(a.Bt16lo)))),
               TT2_ERR_INVALID_ARG, "gemm: Bt16 needs 16-byte alignment, ldbt % 8 == 0 (and Bt16lo for split16 == 1)");
     int sks = 0, skl = 0;
-    static const int sk_mode = [] {  // TT2_GEMM_SKINNY: 2 (default) = register-direct kernel, 1 =
-      const char* e = std::getenv("TT2_GEMM_SKINNY");  // LDS-staged skinny kernel, 0 = gemm_x3_kernel
-      return e ? std::atoi(e) : 2;                     // (A/B: DESIGN §5.6)
-    }();
+    // TT2_GEMM_SKINNY: 2 (default) = register-direct kernel, 1 = LDS-staged skinny kernel,
+    // 0 = gemm_x3_kernel (A/B: DESIGN §5.6)
+    static const int sk_mode = env_int("TT2_GEMM_SKINNY", 2);
     if (sk_mode == 2 && rd_plan(a, sks, skl)) {
       GemmArgs g = a;
       g.ksplit = sks;
@@ -1621,10 +1616,7 @@ int gemm_impl(const GemmArgs& a, hipStream_t s) {
     g.ksplit = 1;
     const long tiles = (long)cdiv(a.N, 128) * cdiv(a.M, 64 * wm16);
     if (a.kpart) {  // split K until ~kTarget work-groups, >= 4 k tiles (128 k) per split
-      static const long kTarget = [] {
-        const char* e = std::getenv("TT2_SPLITK16_TARGET");
-        return e ? std::max(1L, std::atol(e)) : 512L;
-      }();
+      static const long kTarget = std::max(1, env_int("TT2_SPLITK16_TARGET", 512));
       int ks = (int)std::min<long>(kTarget / std::max<long>(tiles, 1), cdiv(a.K, X3_BK) / 4);
       ks = std::max(1, std::min(ks, 256));
       while (ks > 1 && (long)ks * a.M * a.N > a.kpart_floats) --ks;
@@ -1664,10 +1656,7 @@ int gemm_impl(const GemmArgs& a, hipStream_t s) {
   GemmArgs g = a;
   g.ksplit = 1;
   if (a.kpart) {  // split K until ~kTarget work-groups, >= 8 k tiles (128 k) per split
-    static const long kTarget = [] {
-      const char* e = std::getenv("TT2_SPLITK_TARGET");
-      return e ? std::max(1L, std::atol(e)) : 512L;
-    }();
+    static const long kTarget = std::max(1, env_int("TT2_SPLITK_TARGET", 512));
     const long tiles = (long)cdiv(a.M, 64 * wmb) * cdiv(a.N, 64 * wnb);
     const int nkt = cdiv(a.K, 16);
     int ks = (int)std::min<long>(kTarget / std::max<long>(tiles, 1), nkt / 8);

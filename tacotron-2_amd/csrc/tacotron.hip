@@ -41,8 +41,7 @@ static void tt2_fatal_signal(int sig) {
   raise(sig);
 }
 static const bool g_segv_trace = [] {
-  const char* e = std::getenv("TT2_SEGV_TRACE");
-  if (!e || !e[0] || e[0] == '0') return false;
+  if (!env_on("TT2_SEGV_TRACE", false)) return false;
   signal(SIGSEGV, tt2_fatal_signal);
   signal(SIGABRT, tt2_fatal_signal);
   return true;
@@ -1804,8 +1803,7 @@ static void finalize(tt2_ctx* c) {
 // K split of the text-encoder convolutions on the planes path (TT2_ENC_SPLITK, 1..8; default 4)
 constexpr int kEncSplitK = 8;
 static int enc_split_k() {
-  const char* e = std::getenv("TT2_ENC_SPLITK");
-  return e ? std::max(1, std::min(kEncSplitK, std::atoi(e))) : 4;
+  return std::max(1, std::min(kEncSplitK, env_int("TT2_ENC_SPLITK", 4)));
 }
 
 static void alloc_acts(tt2_ctx* c) {
@@ -1873,13 +1871,11 @@ static void alloc_acts(tt2_ctx* c) {
   c->post_b.alloc(B * MF * std::max(c->PC, c->nm) * 4);
   c->mel.alloc(B * MF * c->nm * 4);
   {  // conv_x3 Postnet: TT2_POSTNET_CX=0 selects the im2col GEMMs
-    const char* e = std::getenv("TT2_POSTNET_CX");
-    c->post_cx = (!e || std::atoi(e) != 0) && c->PC % CX_BN == 0 && (cfg.postnet_kernel_size & 1) &&
+    c->post_cx = env_on("TT2_POSTNET_CX", true) && c->PC % CX_BN == 0 && (cfg.postnet_kernel_size & 1) &&
                  cfg.postnet_kernel_size <= 2 * CX_P + 1;
   }
   {  // conv_x3 text encoder: TT2_ENC_CX=0 selects the im2col GEMMs
-    const char* e = std::getenv("TT2_ENC_CX");
-    c->enc_cx = (!e || std::atoi(e) != 0) && c->Cenc % CX_BN == 0 && c->E % 32 == 0 && (8 * c->U) % 4 == 0 &&
+    c->enc_cx = env_on("TT2_ENC_CX", true) && c->Cenc % CX_BN == 0 && c->E % 32 == 0 && (8 * c->U) % 4 == 0 &&
                 (cfg.enc_conv_kernel_size & 1) && cfg.enc_conv_kernel_size <= 2 * CX_P + 1;
   }
   if (c->enc_cx) {
@@ -1986,10 +1982,7 @@ static void encode_dev(tt2_ctx* c, const int* ids_d, const int* lens_d, const in
     a.out = c->enc_out.as<float>(); a.lengths = lens_d; a.B = B; a.T = T; a.Tmax = Tmax;
     a.zo = cfg.zoneout; a.one_m_zo = (float)(1.0 - (double)cfg.zoneout);
     a.err = reinterpret_cast<int*>(a.Hg + 2 * 2 * 32 * ENC_U);
-    {
-      const char* e = std::getenv("TT2_ENC_SENTINEL");
-      a.sentinel = e ? std::atoi(e) : 1;
-    }
+    a.sentinel = env_int("TT2_ENC_SENTINEL", 1);
     void* params[] = {&a};  // cooperative: all 128 work-groups co-resident (h hand-offs spin)
     TT2_HIP(launch_persistent(reinterpret_cast<const void*>(k_enc_bilstm_persist), dim3(2 * ENC_U / 4),
                                        dim3(256), params, 0u, s));
@@ -2178,11 +2171,10 @@ static DecArgs make_dec_args(tt2_ctx* c, int max_iters, const uint8_t* masks_d, 
   a.TP1 = targets_d ? c->TP1.as<float>() : nullptr;
   a.pre1 = c->pre1.as<float>();
   a.masks = masks_d; a.seed = seed; a.targets = targets_d; a.stamps = nullptr;
-  a.stamp_step = -1;
-  if (const char* st = getenv("TT2_STAMP_STEP")) {  // diagnostic: prenet stamps of one decode step
+  a.stamp_step = env_int("TT2_STAMP_STEP", -1);
+  if (!env_str("TT2_STAMP_STEP", "").empty()) {  // diagnostic: prenet stamps of one decode step (negative: every step)
     if (!g_stamps_dev) TT2_HIP(hipMalloc(&g_stamps_dev, 64 * sizeof(long long)));
     a.stamps = g_stamps_dev;
-    a.stamp_step = atoi(st);
   }
   a.frames = frames_d; a.stop = stop_d; a.align = align_d;
   return a;
@@ -2382,7 +2374,7 @@ static void decode_persist_dev(tt2_ctx* c, int max_iters, const uint8_t* masks_d
   a.constraint = cfg.synthesis_constraint; a.monotonic = cfg.constraint_monotonic; a.win = cfg.attention_win_size;
   a.zo = cfg.zoneout; a.one_m_zo = (float)(1.0 - (double)cfg.zoneout);
   a.poll_sleep = 4;
-  if (const char* e = getenv("TT2_PD_SLEEP")) a.poll_sleep = atoi(e);
+  a.poll_sleep = env_int("TT2_PD_SLEEP", a.poll_sleep);
   a.l1_w = c->pd_l1_w.as<float>(); a.l1_wh = c->pd_l1_wh.as<float>(); a.l1_b = c->l1_b.as<float>();  // x KG_SB
   a.l2_w = c->pd_l2_w.as<float>(); a.l2_wh = c->pd_l2_wh.as<float>(); a.l2_b = c->l2_b.as<float>();
   a.GS = c->GS0.as<float>(); a.q_wt = c->q_wt.as<float>(); a.loc_cw = c->loc_cw.as<float>(); a.va = c->va.as<float>();
@@ -2421,12 +2413,11 @@ static void decode_persist_dev(tt2_ctx* c, int max_iters, const uint8_t* masks_d
     a.EMTx = c->EMTx.as<float>();
   }
   a.stamps = nullptr;
-  a.stamp_step = -1;
-  if (const char* st = getenv("TT2_STAMP_STEP")) {  // diagnostic: stage stamps of one decode step
+  a.stamp_step = env_int("TT2_STAMP_STEP", -1);
+  if (a.stamp_step >= 0) {  // diagnostic: stage stamps of one decode step
     if (!g_pd_stamps_dev) TT2_HIP(hipMalloc(&g_pd_stamps_dev, PD_NB * 32 * sizeof(long long)));
     TT2_HIP(hipMemsetAsync(g_pd_stamps_dev, 0, PD_NB * 32 * sizeof(long long), s));
     a.stamps = g_pd_stamps_dev;
-    a.stamp_step = atoi(st);
   }
   TT2_HIP(hipEventRecord(c->pd_ev[0], s));
   pd_launch(a, s, emt, tm);
@@ -2744,11 +2735,11 @@ tt2_status tt2_create(const tt2_config* cfg, int hip_device, tt2_ctx** out) {
     alloc_acts(c.get());
     for (auto& e : c->ev) TT2_HIP(hipEventCreate(&e));
     for (auto& e : c->sev) TT2_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (const char* m = getenv("TT2_DECODER")) c->pd_mode = std::string(m) == "launch" ? 0 : 1;
+    c->pd_mode = env_str("TT2_DECODER", c->pd_mode ? "persist" : "launch") == "launch" ? 0 : 1;
     c->pd_dev_ok = pd_device_ok(hip_device);
-    if (const char* m = getenv("TT2_SIDE_MODE")) c->side_mode = atoi(m);
-    if (const char* m = getenv("TT2_SIDE_DELAY")) c->side_delay = atoi(m);
-    if (const char* m = getenv("TT2_SIDE_DELAY2")) c->side_delay2 = atoi(m);
+    c->side_mode = env_int("TT2_SIDE_MODE", c->side_mode);
+    c->side_delay = env_int("TT2_SIDE_DELAY", c->side_delay);
+    c->side_delay2 = env_int("TT2_SIDE_DELAY2", c->side_delay2);
     *out = c.release();
   });
 }

@@ -20,132 +20,10 @@
 // of the step-t inputs, so a step's carry-ins are read from slot t+1.
 #include <cmath>
 #include <cstring>
-#include <functional>
 
-
-#include "common.h"
-#include "gemm.h"
-#include "train_front.h"
 #include "train_bwd_persist.h"
+#include "train_ctx.h"
 #include "train_persist.h"
-
-namespace tt2 {
-
-struct TrVar {
-  std::string name;
-  std::vector<int64_t> shape;
-  long off = 0, n = 0;
-  bool reg = false;
-};
-
-}  // namespace tt2
-
-using namespace tt2;
-
-struct tt2_train_ctx {
-  int dev = 0;
-  hipStream_t stream = nullptr;
-  tt2_train_config cfg{};
-  int B = 0, Tm = 0, Tin = 0, D = 0, NM = 0, P = 0, H = 0, A = 0, F = 0, KW = 0;
-  int LX1 = 0;  // P + D + H
-  int R = 1;    // outputs_per_step: frames per decoder step
-  std::vector<TrVar> vars;
-  std::map<std::string, int> index;
-  long total = 0;
-  WeightMap host;
-  bool finalized = false;
-  long step_count = 0;
-  // flat parameter / gradient / Adam buffers
-  DevBuf params, grads_own, adam_m, adam_v;
-  float* grads = nullptr;  // grads_own or a caller-bound buffer
-  // transposed weights (refreshed every step)
-  DevBuf K1T, K2T, WqT, WfT, WsT, WmT, Wp2T;
-  // activations
-  DevBuf values, keys, X1, X2, PIN, G1, G2, C1, C2, CN1, CN2, Q, ALIGN, CUM, P1, XIN, FR, ST;
-  // backward
-  DevBuf dFR, dST, dPIN, dX1, dX2, dG1, dG2, DC1, DC2, R1, R2, DQ, DCTX, DKEYS, DCUM;
-  DevBuf dV, dBA, dKC, dBC, DVAL, DMEM, dZ, dPre, TBUF, part, red, kpart;
-  DevBuf DF2, DCUM2, PQ2, SC2;
-  DevBuf DWGP;  // [B][NT][32][A] k_tr_att_bwd_q's d W_loc accumulators (TrAtt::DWGP)
-  DevBuf SS;   // [T][B] smoothing: Σ sigmoid(e) per step (TrAtt::SS)
-  DevBuf DWG;  // [32][A] k_tr_dwloc_cum: Σ cum_{t-1}·du per tap (+ the Σ du row)  // k_tr_att_bwd_q: df / d cum / d query / Σ a·d cum partials by step parity
-  DevBuf TH, E, DF, PQ, FALL, ALN;
-  // the large plain products (tr_gemm_big)
-  DevBuf blasA, blasB, blasP;  // gemm_bf16_kc: bf16 operand copies, split-K partials
-  bool fe_direct = true;  // TT2_FE_CONV_DIRECT=0 at create: the refnet conv2d backward as im2col + GEMM + col2im
-  bool fe_gru_seq = true;  // TT2_FE_GRU_SEQ=0 at create: the refnet GRU as per-step launches (4 per step)
-  bool blas_on = true;  // TT2_TRAIN_BLAS=0 at create: the large products on gemm_x3_kernel too
-  long blas_calls = 0;
-  // bf16 copies of the recurrent weights in both layouts (precision = bf16), refreshed per step
-  DevBuf hK1, hK1T, hK2, hK2T, hWq, hWqT;
-  DevBuf X1h, X2h;  // bf16 shadows of the X1 / X2 rows (inputs of the fused LSTM products)
-  DevBuf dGh;       // bf16 shadows of one step's dG2 | dG1 rows (fused backward products)
-  DevBuf tK1T, tK2T, tWq, tK2, tK1;  // the fused products' weights in TF layout (k_tr_tf_weights)
-  // Postnet training (cfg.postnet): PA[i] activations (pre-BN), PX[i] layer inputs (PX[0] unused:
-  // layer 1 reads the clipped frames), batch stats, projection, scratch
-  DevBuf PA[8], PX[9];  // postnet_layers <= 8
-  DevBuf BNM, BNV, PPRJ, dPP, DYb, DZb, dPXa, dPXb, WFLIP, PWT, CLIPM, pn_part;
-  int PL = 0, PC = 0, PK = 0;
-  bool pn_masks = false;
-  int T_last = 0, Tin_last = 0;  // decoder steps / encoder positions of the last forward_backward
-  int Tf_last = 0;               // its frame count T_last * R
-  DevBuf FRT;                    // R > 1: the clipped frames time-major [T_f][B][NM] (the Postnet's input)
-  bool pn_ran = false;  // batch stats of the last forward are valid (moving averages in apply)
-  // bf16 Postnet convolutions over padded planes (gemm.h conv_bf16_planes): the layer input / dz
-  // planes (pad rows zeroed when the shape changes) and the transposed bf16 weights of one layer
-  DevBuf pnPl, pnWt;
-  DevBuf fePl, feWt;  // the same for the text encoder's convolutions (TT2_PN_PLANES gates both)
-  int fe_pl_B = -1, fe_pl_T = -1;
-  DevBuf values16;         // bf16 values for the per-step context / d align reads (TT2_TR_VALUES16)
-  bool values16_on = true;
-  int pn_pl_B = -1, pn_pl_T = -1;
-  bool pn_planes = false;
-  hipStream_t last_stream = nullptr;  // stream of the last forward_backward / apply (read-backs)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  float last_ms = 0.f;
-  // front end (cfg.frontend: encoder + reference encoders + GST, train_front.hip)
-  int f_nref = 0, f_gin = 0, f_T2 = 0, f_T2max = 0;
-  bool f_ran = false;
-  // cfg.adain (ReferenceEncoderAdaIn, modules.py:66-107): stacks r = 0 (emotion mel) and r = 1 (speaker
-  // mel) without batch norm, the speaker map restyled by the emotion map's moments, one GRU + dense
-  // (r = 1 buffers): fADX the restyled map (GRU input), fADM moments [2 (emt, spk)][B][C][2], fADS the
-  // backward's per-channel sums, fDYE the emotion stack's map gradient
-  bool f_adain = false;
-  DevBuf fADX, fADM, fADS, fDYE;
-  DevBuf fTWf, fTWb, fHSh, fDZh;  // encoder BiLSTM fused steps: TF-layout weights and state / dZ shadows
-  DevBuf fEX, fEA[8], fEY[9], fXP, fGZ, fGA, fCN, fCS, fHS, fENC, fMEM, fSTY, fDSTY, fDZ, fDHC, fDCC, fDHP, fdXP, fdA,
-      fdB, fLWxT, fLWhT;
-  DevBuf fRA[2][6], fRY[2][6], fXG[2], fGR[2], fGU[2], fGCC[2], fGRH[2], fHG[2], fREF[2], fGG, fGC, fFBUF, fDY, fDY2,
-      fDZc;
-  DevBuf fGq, fGkk, fGv, fGnv, fGbb, fGsum, fdREF, fDZD, fDH, fDHA, fDRH, fDCP, fDGP, fDXG, fWT, fBN, fpart;
-  // loss masks (cfg.mask_decoder): target lengths [B] on the device, their sum
-  DevBuf TLEN;
-  bool has_tlen = false;
-  // style-embedding losses (cfg.n_emt / n_spk / orthog_weight): labels [2][B], the extra d refnet
-  // outputs [2][B][128], classifier logit gradients [B][max(n)], the orthogonality product [B][B]
-  DevBuf sLAB, sXREF, sDL, sOM;
-  bool has_labels = false;
-  long tlen_sum = 0;
-  int tlen_max = 0;
-  // teacher-forcing draw (tt2_train_set_teacher_forcing): feed[t] = 1 target frame t-1, 0 own frame
-  std::vector<uint8_t> feed;
-  // free-running steps: prenet-1 kernel transposed [P][NM], per-step scratch
-  DevBuf W1T, sDZ, sDP, sDX;
-  // persistent forward (train_persist.hip; TT2_TR_PERSIST=0 keeps the per-step launches): exchange
-  // buffers, energy granules, flags + control words, the prenet rows in bf16 fragment layout
-  DevBuf tpCX, tpH1X, tpZ1X, tpH2X, tpZ2X, tpEX, tpCtl, tpPre, tpStamps, tpKWT;
-  bool tp_on = false, tp_last = false, tp_check = false;
-  // persistent backward (train_bwd_persist.hip): exchange buffers, flags + control words
-  DevBuf tbG1X, tbG2X, tbP1X, tbP2X, tbQX, tbCtl, tbW1F, tbPK, tbDGT1, tbDGT2, tbDGR1;
-  DevBuf reg_segs;  // [nreg] (offset, size) of the regularised variables (tr_regularize)
-  int nreg = 0;
-  bool tb_dgt = false;  // the last persistent backward wrote bf16(dG)^T for the weight-gradient GEMMs
-  bool tb_dgr = false;  // ... and bf16(dG1) row-major for the d X1 product
-  bool tb_on = false, tb_last = false, tb_check = false;
-  int* tb_ctl_dev = nullptr;
-  int* tp_ctl_dev = nullptr;  // control words of the last persistent forward (device)
-  int* tp_ctl_host = nullptr;  // pinned [2]: the launch's control words, checked at the next read-back
-};
 
 namespace tt2 {
 
@@ -407,7 +285,6 @@ __global__ void k_tr_lstm_fwd(TrLstmFwd a) {
 //   TF_PLAIN C = X·W + residual (d X1 = dG1 · K1^T + R1)
 // A operands are bf16 shadows of the fp32 rows written by their producers (same round-to-nearest-
 // even as the staged operands of the bf16 GEMMs), except TF_BWD_H's.
-enum { TF_FWD = 0, TF_BWD_H = 1, TF_BWD_S = 2, TF_PLAIN = 3, TF_EFWD = 4, TF_EBWD = 5 };
 // Fragment-major bf16 layout of a [rows][K] operand ("TF layout"): 32-row blocks x 16-deep k-steps x
 // [32 rows][16 k], so one wave's v_mfma_f32_32x32x16_bf16 fragment load of a k-step (lane l: row l%32,
 // k = 8(l/32) .. +8) is ONE contiguous kilobyte instead of 32 rows a K-stride apart.  The weights are
@@ -443,65 +320,7 @@ __global__ void k_tr_tf_weights_f32(const float* __restrict__ src, long ld, int 
     dst[tf_sw(r, k, K)] = col < N ? (__bf16)(transposed ? src[(long)k * ld + col] : src[col * ld + k]) : (__bf16)0.f;
   }
 }
-constexpr int TLG_U = 8, TLG_NT = 512, TLG_KSMAX = 16;
 typedef float tlg_f32x16 __attribute__((ext_vector_type(16)));
-struct TrFused {
-  const __bf16* Ah;  // this step's bf16 input rows, TF layout of width K, or
-  const float* Af;   // fp32 input rows (TF_BWD_H)
-  long lda;
-  int af_parts;      // > 1: each Af row is the sum of af_parts partial rows af_pstride apart (in order)
-  int af_pstride;
-  const __bf16* Wt;  // W^T in TF layout, column-group order (k_tr_tf_weights)
-  int K, B, H, N;
-  int t, layer;
-  float z;
-  const uint8_t* zm;     // [T][4][B][H] zoneout keep masks or null
-  const float* G;        // fwd: out [B][4H] activated gates; bwd: in
-  const float* bias;     // fwd
-  const float* c_prev;   // [B,H]
-  const float* hz_prev;  // fwd, strided
-  long ld_hz_prev;
-  float* cn;             // fwd out / bwd in [B,H]
-  float* c_out;          // fwd [B,H]
-  float* h_out;          // fwd strided h_new
-  long ld_h;
-  float* hz_out;         // fwd strided zoned h
-  long ld_hz;
-  __bf16* h_out_h;       // fwd bf16 TF-layout shadows (step block base, width ld_*_h, column offset
-  long ld_h_h;           // *_col0) or null
-  __bf16* hz_out_h;
-  long ld_hz_h;
-  int h_col0, hz_col0;
-  const float* dh_ext;   // bwd: d h_new from the frame projection (strided) or null
-  long ld_dh;
-  float* side;           // TF_BWD_S: d hz2_{t-1} out (strided), = product + side_res[.][H + n]
-  long ld_side;
-  const float* side_res;
-  long ld_side_res;
-  const float* dhz;      // bwd: d(zoned h_t) from step t+1 (strided)
-  long ld_dhz;
-  float* DC;             // bwd [B,H] in/out
-  float* dG;             // bwd out [B][4H]
-  __bf16* dGh;           // bwd bf16 shadow of dG or null
-  float* R;              // bwd [B][ldr] at off_r + n
-  long ldr;
-  int off_r;
-  float* C;              // TF_PLAIN out (ld ldc) = product + residual
-  long ldc;
-  const float* residual;
-  long ldres;
-  // encoder BiLSTM (TF_EFWD / TF_EBWD, FeLstm's buffers; H = U, both directions in one launch)
-  const int* lens;
-  int T;                 // encoder steps
-  float zo;
-  long wdir, adir;       // per-direction strides of Wt and of the bf16 state shadow (elements)
-  const float* XP;       // [B][T][8U] input projections (+ bias)
-  float* GA; float* CN; float* CS; float* HS; float* ENC;
-  __bf16* HSh;           // [2][T+1][Bp][U] TF layout: h state shadow (EFWD: A operand and output)
-  const float* DENC; long ld_denc;
-  float* DZ; float* DCC; float* DHP;
-  __bf16* DZh;           // [2 dirs][2 slots][Bp][4U] TF layout: dZ shadow (EBWD: A of step t-1)
-};
 
 // Epilogue operands of one (row, unit), loaded BEFORE the product so their round trip overlaps the
 // operand stream instead of following the reduction barrier.
@@ -2303,7 +2122,7 @@ __global__ void k_tr_zero_many(TrZeroList z) {
     }
   }
 }
-static void tr_zero_many(std::initializer_list<std::pair<void*, size_t>> l, hipStream_t s) {
+void tr_zero_many(std::initializer_list<std::pair<void*, size_t>> l, hipStream_t s) {
   TrZeroList z{};
   unsigned long long tot = 0;
   for (const auto& e : l) {
@@ -2405,11 +2224,6 @@ __global__ __launch_bounds__(TR_FIN) void k_pn_colstat_final(const float* __rest
 }
 // y = gamma (a - mean) rsqrt(var + eps) + beta, then dropout(0.5) with keep bits (or identity)
 // planes (nullable): the next conv's padded bf16 input (gemm.h CX_* layout, rows b·T + t of y)
-__device__ __forceinline__ void pn_plane_put(__bf16* planes, int T, long i, int C, float v) {
-  const long m = i / C;
-  const int c = (int)(i - m * C), b = (int)(m / T), t = (int)(m - (long)b * T);
-  planes[(CX_G + (long)b * (T + 2 * CX_P) + CX_P + t) * C + c] = (__bf16)v;
-}
 __global__ void k_pn_bn_fwd(const float* __restrict__ a, long M, int C, const float* __restrict__ mean,
                             const float* __restrict__ var, const float* __restrict__ gamma,
                             const float* __restrict__ beta, float eps, const uint8_t* __restrict__ keep,
@@ -2566,14 +2380,12 @@ __global__ void k_tr_status(const int* __restrict__ ctl, const int* __restrict__
 }
 
 // ---- host orchestration ----------------------------------------------------------------------
-static inline unsigned nblk(long n, int t = 256) { return (unsigned)((n + t - 1) / t); }
-
-static void tr_transpose(const float* src, long rows, long cols, long lds, float* dst, long ldd, hipStream_t s) {
+void tr_transpose(const float* src, long rows, long cols, long lds, float* dst, long ldd, hipStream_t s) {
   dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));
   hipLaunchKernelGGL(k_tr_transpose, grid, dim3(256), 0, s, src, rows, cols, lds, dst, ldd);
 }
 
-static void tr_colsum(tt2_train_ctx* c, const float* in, long M, int N, long ld, float* out, hipStream_t s) {
+void tr_colsum(tt2_train_ctx* c, const float* in, long M, int N, long ld, float* out, hipStream_t s) {
   const int S = tr_splits(M, N, 64 * std::max<long>(4L * c->H, c->LX1));
   TT2_CHECK((size_t)S * N * sizeof(float) <= c->part.bytes, TT2_ERR_SHAPE_MISMATCH, "tr_colsum: partial buffer too small");
   hipLaunchKernelGGL(k_tr_colsum_part, dim3((N + tr_tw(N) - 1) / tr_tw(N), S), dim3(256), 0, s, in, M, N, ld,
@@ -2581,12 +2393,59 @@ static void tr_colsum(tt2_train_ctx* c, const float* in, long M, int N, long ld,
   hipLaunchKernelGGL(k_tr_colsum_final, dim3((N + 31) / 32), dim3(TR_FIN), 0, s, c->part.as<float>(), S, N, out);
 }
 
-// per calling thread: the context a tt2_train_* call is driving (a call runs on one thread, so
-// distinct contexts driven from different threads stay independent)
-static thread_local DevBuf* g_tr_kpart = nullptr;  // split-K scratch (stream-ordered)
-static thread_local int g_tr_prec = 0;             // GemmArgs::split16 (0 fp32, 2 bf16)
-static thread_local tt2_train_ctx* g_tr_ctx = nullptr;  // bf16 BLAS scratch + handle of that context
-
+// Training-mode batch norm over the M rows of [M][C] (Postnet, encoder convs, reference encoders).
+// cap bounds the row splits (tr_splits) to what `part` holds: 2 x cap floats.
+void tr_bn_stats(const float* x, long M, int C, long cap, float* part, float* mean, float* var, hipStream_t s) {
+  const int S = tr_splits(M, C, cap);
+  const dim3 grid((unsigned)((C + tr_tw(C) - 1) / tr_tw(C)), S);
+  hipLaunchKernelGGL(k_pn_colstat_part, grid, dim3(256), 0, s, x, M, C, nullptr, 0, part);
+  hipLaunchKernelGGL(k_pn_colstat_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, 1.0f / (float)M, mean);
+  hipLaunchKernelGGL(k_pn_colstat_part, grid, dim3(256), 0, s, x, M, C, mean, 1, part);
+  hipLaunchKernelGGL(k_pn_colstat_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, 1.0f / (float)M, var);
+}
+void tr_bn_fwd(const float* a, long M, int C, const float* mean, const float* var, const float* gamma,
+               const float* beta, float eps, const uint8_t* keep, float* y, __bf16* planes, int T, hipStream_t s) {
+  hipLaunchKernelGGL(k_pn_bn_fwd, dim3(nblk(M * C)), dim3(256), 0, s, a, M, C, mean, var, gamma, beta, eps, keep, y,
+                     planes, T);
+}
+// dxn (through the dropout keep bits) -> dy, d gamma / d beta (written) and dz through act' of a
+// (0 none, 1 tanh', 2 relu'); sums: 2 x C floats of scratch
+void tr_bn_bwd(const float* dxn, const uint8_t* keep, const float* a, long M, int C, const float* mean,
+               const float* var, float eps, const float* gamma, float* dgamma, float* dbeta, long cap, float* part,
+               float* sums, int act, float* dy, float* dz, __bf16* planes, int T, hipStream_t s) {
+  const int S = tr_splits(M, C, cap);
+  hipLaunchKernelGGL(k_pn_bn_bwd_part, dim3((unsigned)((C + tr_tw(C) - 1) / tr_tw(C)), S), dim3(256), 0, s, dxn, keep,
+                     a, M, C, mean, var, eps, dy, part);
+  hipLaunchKernelGGL(k_pn_bn_bwd_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, sums, dgamma, dbeta);
+  hipLaunchKernelGGL(k_pn_bn_bwd_dz, dim3(nblk(M * C)), dim3(256), 0, s, dy, a, M, C, mean, var, eps, gamma, sums, act,
+                     dz, planes, T);
+}
+void tr_im2col_t(const float* x, long xs_b, long xs_t, int B, int T, int C, int kw, int pad, float* out, long M,
+                 hipStream_t s) {
+  hipLaunchKernelGGL(k_pn_im2col_t, dim3(nblk((long)kw * C * M)), dim3(256), 0, s, x, xs_b, xs_t, B, T, C, kw, pad, out,
+                     M);
+}
+void tr_conv_flip(const float* w, int kw, int cin, int cout, float* wf, hipStream_t s) {
+  hipLaunchKernelGGL(k_pn_flip, dim3(nblk((long)kw * cin * cout)), dim3(256), 0, s, w, kw, cin, cout, wf);
+}
+void tr_rows_copy(const float* src, long lds, long rows, int cols, float* dst, long ldd, const float* add, long lda,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(k_tr_rows_copy, dim3(nblk(rows * cols)), dim3(256), 0, s, src, lds, rows, cols, dst, ldd, add,
+                     lda);
+}
+void tr_sum_final(const float* part, int nb, float scale, float* out, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(k_tr_sum_final, dim3(1), dim3(256), 0, s, part, nb, scale, out, mode);
+}
+void tr_tf_weights_f32(const float* src, long ld, int transposed, int N, int K, int ncg, int mode, int H, __bf16* dst,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(k_tr_tf_weights_f32, dim3(1024), dim3(256), 0, s, src, ld, transposed, N, K, ncg, mode, H, dst);
+}
+void tr_fused_enc_step(const TrFused& e, bool backward, hipStream_t s) {  // H = U units, both directions
+  if (backward)
+    hipLaunchKernelGGL(k_tr_fused<TF_EBWD>, dim3(2 * 2 * e.H / 32), dim3(TLG_NT), 0, s, e);
+  else
+    hipLaunchKernelGGL(k_tr_fused<TF_EFWD>, dim3(2 * 2 * e.H / 8), dim3(TLG_NT), 0, s, e);
+}
 
 // fp32 [rows][cols] (leading dimension ld) -> dense bf16 [rows][cols], round to nearest even (the
 // same rounding the bf16 GEMM kernels apply when they stage operands)
@@ -2614,87 +2473,67 @@ __global__ void k_tr_to_bf16(const float* __restrict__ src, long rows, long cols
 // the same operand rounding as the per-step bf16 kernels.  Products below kTrBigMinFlops keep the
 // per-step kernels' paths, except tall ones (>= 16k rows, N >= 256, K >= 64: e.g. d [h2 | ctx] =
 // d frames · W_f^T over all T·B rows, bound by its output, which gemm_x3_kernel wrote at 0.6 TB/s).
-static constexpr double kTrBigMinFlops = 2.0e10;
-static bool tr_gemm_big(int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, float* C, long ldc,
-                        hipStream_t s) {
-  tt2_train_ctx* c = g_tr_ctx;
-  if (!c) return false;
+bool tr_gemm_big(tt2_train_ctx* c, int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, float* C,
+                 long ldc, hipStream_t s) {
   gemm_bf16_kc(M, N, K, A, lda, Bw, ldb, C, ldc, c->blasA, c->blasB, c->blasP, s);
   ++c->blas_calls;
   return true;
 }
 
-static void tr_gemm(int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, float* C, long ldc,
-                    hipStream_t s, const float* bias, const float* residual, long ldr, int act, const DevBuf* bt16,
-                    long ldbt);
-
 // Weight gradient C[M][N] = X^T·dG over K = T·B rows, X[K][M] (row stride ldx), dG[K][N]: the large
 // ones straight from X on gemm_bf16_kc (its conversion pass transposes X), the rest through
 // tr_transpose into TBUF and tr_gemm
-static void tr_gemm_xtg(int M, int N, int K, const float* X, long ldx, const float* dG, long ldg, float* C, long ldc,
-                        float* TBUF, hipStream_t s, const __bf16* dgt = nullptr) {
-  tt2_train_ctx* c = g_tr_ctx;
-  if (c && c->blas_on && g_tr_prec == 2 && 2.0 * M * (double)N * K >= kTrBigMinFlops) {
+void tr_gemm_xtg(tt2_train_ctx* c, int M, int N, int K, const float* X, long ldx, const float* dG, long ldg, float* C,
+                 long ldc, float* TBUF, hipStream_t s, const __bf16* dgt) {
+  if (c->sw.blas && tr_prec(c) == 2 && 2.0 * M * (double)N * K >= kTrBigMinFlops) {
     // dgt: bf16(dG)^T already staged by the persistent backward (gemm_bf16_kc bt_pre)
     gemm_bf16_kc(M, N, K, X, ldx, dG, ldg, C, ldc, c->blasA, c->blasB, c->blasP, s, true, nullptr, dgt);
     ++c->blas_calls;
     return;
   }
   tr_transpose(X, K, M, ldx, TBUF, K, s);
-  tr_gemm(M, N, K, TBUF, K, dG, ldg, C, ldc, s, nullptr, nullptr, 0, ACT_NONE, nullptr, 0);
+  tr_gemm(c, M, N, K, TBUF, K, dG, ldg, C, ldc, s);
 }
 
-static void tr_gemm(int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, float* C, long ldc,
-                    hipStream_t s, const float* bias = nullptr, const float* residual = nullptr, long ldr = 0,
-                    int act = ACT_NONE, const DevBuf* bt16 = nullptr, long ldbt = 0) {
-  if (g_tr_ctx && g_tr_ctx->blas_on && g_tr_prec == 2 && !bias && !residual && act == ACT_NONE &&
+void tr_gemm(tt2_train_ctx* c, int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, float* C,
+             long ldc, hipStream_t s, const float* bias, const float* residual, long ldr, int act, const DevBuf* bt16,
+             long ldbt) {
+  if (c->sw.blas && tr_prec(c) == 2 && !bias && !residual && act == ACT_NONE &&
       (2.0 * M * (double)N * K >= kTrBigMinFlops || (M >= 16384 && N >= 256 && K >= 64)) &&
-      tr_gemm_big(M, N, K, A, lda, Bw, ldb, C, ldc, s))
+      tr_gemm_big(c, M, N, K, A, lda, Bw, ldb, C, ldc, s))
     return;
   GemmArgs g;
-  if (g_tr_prec == 2 && bt16 && bt16->p && ldbt % 8 == 0) {  // weights pre-converted: B^T in bf16
+  if (tr_prec(c) == 2 && bt16 && bt16->p && ldbt % 8 == 0) {  // weights pre-converted: B^T in bf16
     g.Bt16 = bt16->p;
     g.ldbt = ldbt;
-  }
-  if (g_tr_kpart) {
-    g.kpart = g_tr_kpart->as<float>();
-    g.kpart_floats = (long)(g_tr_kpart->bytes / sizeof(float));
   }
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.Bw = Bw; g.ldb = ldb; g.Cout = C; g.ldc = ldc;
   g.bias = bias; g.residual = residual; g.ldr = ldr; g.act = act;
-  g.split16 = g_tr_prec;
-  gemm(g, s);
+  tr_gemm_run(c, g, s);
 }
 
 // raw split-K product for a fused combine: partials [ks][M][N] in the context's kpart; returns ks
-static int tr_gemm_raw(int M, int N, int K, const float* A, long lda, const float* Bw, long ldb, hipStream_t s,
-                       const DevBuf* bt16 = nullptr, long ldbt = 0) {
+int tr_gemm_raw(tt2_train_ctx* c, int M, int N, int K, const float* A, long lda, const float* Bw, long ldb,
+                hipStream_t s, const DevBuf* bt16, long ldbt) {
   GemmArgs g;
-  if (g_tr_prec == 2 && bt16 && bt16->p && ldbt % 8 == 0) {
+  if (tr_prec(c) == 2 && bt16 && bt16->p && ldbt % 8 == 0) {
     g.Bt16 = bt16->p;
     g.ldbt = ldbt;
   }
-  g.kpart = g_tr_kpart->as<float>();
-  g.kpart_floats = (long)(g_tr_kpart->bytes / sizeof(float));
+  g.kpart = c->kpart.as<float>();
+  g.kpart_floats = (long)(c->kpart.bytes / sizeof(float));
   g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.Bw = Bw; g.ldb = ldb; g.Cout = nullptr; g.ldc = N;
-  g.split16 = g_tr_prec;
+  g.split16 = tr_prec(c);
   return gemm_raw(g, s);
 }
 
-static void tr_gemm_run(GemmArgs& g, hipStream_t s) {  // conv-mode products: same precision / split-K
-  if (g_tr_kpart) {
-    g.kpart = g_tr_kpart->as<float>();
-    g.kpart_floats = (long)(g_tr_kpart->bytes / sizeof(float));
-  }
-  g.split16 = g_tr_prec;
+void tr_gemm_run(tt2_train_ctx* c, GemmArgs& g, hipStream_t s) {  // any product: the context's precision / split-K scratch
+  g.kpart = c->kpart.as<float>();
+  g.kpart_floats = (long)(c->kpart.bytes / sizeof(float));
+  g.split16 = tr_prec(c);
   gemm(g, s);
 }
 
-static float* pvar(tt2_train_ctx* c, const std::string& n) { return c->params.as<float>() + c->vars[c->index.at(n)].off; }
-static float* gvar(tt2_train_ctx* c, const std::string& n) { return c->grads + c->vars[c->index.at(n)].off; }
-
-static const char* TP = "Tacotron_model/inference/";
-static std::string vn(const char* s) { return std::string(TP) + s; }
 #define LAV(x) vn("decoder/Location_Sensitive_Attention/" x)
 #define L1V(x) vn("decoder/decoder_LSTM/multi_rnn_cell/cell_0/lstm_cell/" x)
 #define L2V(x) vn("decoder/decoder_LSTM/multi_rnn_cell/cell_1/lstm_cell/" x)
@@ -2734,14 +2573,11 @@ static std::string tr_bufname(const void* owner, const DevBuf* b) {
   return "";
 }
 // TT2_REDZONE: fail the call naming every buffer a kernel of this phase wrote past
-static void tr_redzones(tt2_train_ctx* c, const char* phase) {
+void tr_redzones(tt2_train_ctx* c, const char* phase) {
   if (!redzone_on()) return;
   const std::string r = redzone_check(phase, tr_bufname, c);
   TT2_CHECK(r.empty(), TT2_ERR_HIP, "redzone violation: " + r);
 }
-
-static void tr_front_build_vars(tt2_train_ctx* c,
-                                const std::function<void(const std::string&, std::vector<int64_t>, bool)>& add);
 
 static void tr_build_vars(tt2_train_ctx* c) {
   const int D = c->D, A = c->A, F = c->F, KW = c->KW, P = c->P, H = c->H, NM = c->NM;
@@ -2798,8 +2634,6 @@ static void tr_build_vars(tt2_train_ctx* c) {
 static std::string pn_scope(int i) {
   return vn("postnet_convolutions/conv_layer_") + std::to_string(i) + "_postnet_convolutions/";
 }
-
-static void tr_front_alloc(tt2_train_ctx* c);
 
 static void tr_alloc(tt2_train_ctx* c) {
   const long B = c->B, T = c->Tm, Tin = c->Tin, D = c->D, H = c->H, P = c->P, A = c->A, F = c->F, KW = c->KW,
@@ -2862,10 +2696,7 @@ static void tr_alloc(tt2_train_ctx* c) {
     f(c->DYb, TB * PC); f(c->DZb, TB * PC); f(c->dPXa, TB * std::max(PC, NM)); f(c->dPXb, TB * std::max(PC, NM));
     f(c->WFLIP, PK * std::max(PC, NM) * PC);  // flipped kernels: layer 1's are [PK][num_mels][PC]
     f(c->PWT, NM * PC); f(c->pn_part, 64 * 2 * PC + 1024);
-    {
-      const char* e = std::getenv("TT2_PN_PLANES");  // 0: the implicit-im2col gemm_x3_kernel convs
-      c->pn_planes = (!e || std::atoi(e) != 0) && c->cfg.precision && PC % 64 == 0 && (PK & 1) && PK <= 2 * CX_P + 1;
-    }
+    c->pn_planes = c->sw.pn_planes && c->cfg.precision && PC % 64 == 0 && (PK & 1) && PK <= 2 * CX_P + 1;
     if (c->pn_planes) {
       const long W = std::max<long>(PC, NM), Wr = (W + 255) / 256 * 256;
       c->pnPl.alloc((size_t)cx_rows(c->B, (int)(TB / c->B)) * PC * 2);
@@ -2888,12 +2719,6 @@ static void tr_postnet(tt2_train_ctx* c, const float* tg, const uint8_t* pnm, in
   float* part = c->pn_part.as<float>();
   float* sums = part + 64L * 2 * C;
   float* TBUF = c->TBUF.as<float>();
-  const int S = tr_splits(M, C, 64L * C);
-  const unsigned CT = (unsigned)((C + tr_tw(C) - 1) / tr_tw(C));
-  auto colstat = [&](const float* x, const float* ctr, int mode, float* out) {
-    hipLaunchKernelGGL(k_pn_colstat_part, dim3(CT, S), dim3(256), 0, s, x, M, C, ctr, mode, part);
-    hipLaunchKernelGGL(k_pn_colstat_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, 1.0f / (float)M, out);
-  };
   auto conv_in = [&](int i, GemmArgs& g) {  // layer i's input as an implicit-im2col conv1d operand
     if (i == 0) {  // clipped decoder frames, time-major [T][B][NM] (r > 1: the FRT copy)
       g.A = c->R > 1 ? c->FRT.as<float>() : c->FR.as<float>(); g.C = NM; g.xs_b = NM; g.xs_t = (long)B * NM;
@@ -2901,7 +2726,7 @@ static void tr_postnet(tt2_train_ctx* c, const float* tg, const uint8_t* pnm, in
       g.A = c->PX[i].as<float>(); g.C = C; g.xs_b = (long)T * C; g.xs_t = C;
     }
   };
-  const bool planes = c->pn_planes && g_tr_prec == 2;
+  const bool planes = c->pn_planes && tr_prec(c) == 2;
   __bf16* pl = reinterpret_cast<__bf16*>(c->pnPl.p);
   __bf16* wt = reinterpret_cast<__bf16*>(c->pnWt.p);
   if (planes && (c->pn_pl_B != B || c->pn_pl_T != T)) {  // pad and guard rows stay zero from here on
@@ -2926,19 +2751,17 @@ static void tr_postnet(tt2_train_ctx* c, const float* tg, const uint8_t* pnm, in
       g.K = KW * g.C;
       g.Bw = pvar(c, sc + "conv1d/kernel"); g.ldb = C; g.Cout = c->PA[i].as<float>(); g.ldc = C;
       g.bias = pvar(c, sc + "conv1d/bias"); g.act = i < L - 1 ? ACT_TANH : ACT_NONE;
-      tr_gemm_run(g, s);
+      tr_gemm_run(c, g, s);
     }
     float* mean = c->BNM.as<float>() + (long)i * C;
     float* var = c->BNV.as<float>() + (long)i * C;
-    colstat(c->PA[i].as<float>(), nullptr, 0, mean);
-    colstat(c->PA[i].as<float>(), mean, 1, var);
-    hipLaunchKernelGGL(k_pn_bn_fwd, dim3(nblk(M * C)), dim3(256), 0, s, c->PA[i].as<float>(), M, C, mean, var,
-                       pvar(c, sc + "batch_normalization/gamma"), pvar(c, sc + "batch_normalization/beta"), eps,
-                       pnm ? pnm + (long)i * M * C : nullptr, c->PX[i + 1].as<float>(),
-                       planes && i < L - 1 ? pl : nullptr, T);
+    tr_bn_stats(c->PA[i].as<float>(), M, C, 64L * C, part, mean, var, s);
+    tr_bn_fwd(c->PA[i].as<float>(), M, C, mean, var, pvar(c, sc + "batch_normalization/gamma"),
+              pvar(c, sc + "batch_normalization/beta"), eps, pnm ? pnm + (long)i * M * C : nullptr,
+              c->PX[i + 1].as<float>(), planes && i < L - 1 ? pl : nullptr, T, s);
   }
   const std::string pp = vn("postnet_projection/projection_postnet_projection/");
-  tr_gemm((int)M, NM, C, c->PX[L].as<float>(), C, pvar(c, pp + "kernel"), NM, c->PPRJ.as<float>(), NM, s,
+  tr_gemm(c, (int)M, NM, C, c->PX[L].as<float>(), C, pvar(c, pp + "kernel"), NM, c->PPRJ.as<float>(), NM, s,
           pvar(c, pp + "bias"));
   const int* tlen = c->cfg.mask_decoder ? c->TLEN.as<int>() : nullptr;
   const double nmse = c->cfg.mask_decoder ? (double)c->tlen_sum * NM : (double)M * NM;
@@ -2949,43 +2772,37 @@ static void tr_postnet(tt2_train_ctx* c, const float* tg, const uint8_t* pnm, in
                      red + 4, 0);
   // backward: projection
   tr_transpose(c->PX[L].as<float>(), M, C, C, TBUF, M, s);
-  tr_gemm(C, NM, (int)M, TBUF, M, c->dPP.as<float>(), NM, gvar(c, pp + "kernel"), NM, s);
+  tr_gemm(c, C, NM, (int)M, TBUF, M, c->dPP.as<float>(), NM, gvar(c, pp + "kernel"), NM, s);
   tr_colsum(c, c->dPP.as<float>(), M, NM, NM, gvar(c, pp + "bias"), s);
   tr_transpose(pvar(c, pp + "kernel"), C, NM, NM, c->PWT.as<float>(), C, s);
   float* dxn = c->dPXa.as<float>();
   float* dxo = c->dPXb.as<float>();
-  tr_gemm((int)M, C, NM, c->dPP.as<float>(), NM, c->PWT.as<float>(), C, dxn, C, s);
+  tr_gemm(c, (int)M, C, NM, c->dPP.as<float>(), NM, c->PWT.as<float>(), C, dxn, C, s);
   for (int i = L - 1; i >= 0; --i) {
     const std::string sc = pn_scope(i + 1);
     const float* mean = c->BNM.as<float>() + (long)i * C;
     const float* var = c->BNV.as<float>() + (long)i * C;
-    hipLaunchKernelGGL(k_pn_bn_bwd_part, dim3(CT, S), dim3(256), 0, s, dxn,
-                       pnm ? pnm + (long)i * M * C : nullptr, c->PA[i].as<float>(), M, C, mean, var, eps,
-                       c->DYb.as<float>(), part);
-    hipLaunchKernelGGL(k_pn_bn_bwd_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, sums,
-                       gvar(c, sc + "batch_normalization/gamma"), gvar(c, sc + "batch_normalization/beta"));
-    hipLaunchKernelGGL(k_pn_bn_bwd_dz, dim3(nblk(M * C)), dim3(256), 0, s, c->DYb.as<float>(), c->PA[i].as<float>(),
-                       M, C, mean, var, eps, pvar(c, sc + "batch_normalization/gamma"), sums, i < L - 1 ? 1 : 0,
-                       c->DZb.as<float>(), planes ? pl : nullptr, T);
+    tr_bn_bwd(dxn, pnm ? pnm + (long)i * M * C : nullptr, c->PA[i].as<float>(), M, C, mean, var, eps,
+              pvar(c, sc + "batch_normalization/gamma"), gvar(c, sc + "batch_normalization/gamma"),
+              gvar(c, sc + "batch_normalization/beta"), 64L * C, part, sums, i < L - 1 ? 1 : 0, c->DYb.as<float>(),
+              c->DZb.as<float>(), planes ? pl : nullptr, T, s);
     tr_colsum(c, c->DZb.as<float>(), M, C, C, gvar(c, sc + "conv1d/bias"), s);
     const int cin = i == 0 ? NM : C;
     {
       GemmArgs gi;
       conv_in(i, gi);
-      if (c->blas_on && g_tr_prec == 2 && 2.0 * KW * cin * (double)C * M >= kTrBigMinFlops) {
+      if (c->sw.blas && tr_prec(c) == 2 && 2.0 * KW * cin * (double)C * M >= kTrBigMinFlops) {
         KcConvA cv;  // im2colᵀ gathered straight into gemm_bf16_kc's bf16 operand copy
         cv.x = gi.A; cv.xs_b = gi.xs_b; cv.xs_t = gi.xs_t; cv.B = B; cv.T = T; cv.C = cin; cv.kw = KW; cv.pad = pad;
         gemm_bf16_kc(KW * cin, C, (int)M, nullptr, 0, c->DZb.as<float>(), C, gvar(c, sc + "conv1d/kernel"), C,
                      c->blasA, c->blasB, c->blasP, s, false, &cv);
         ++c->blas_calls;
       } else {
-        hipLaunchKernelGGL(k_pn_im2col_t, dim3(nblk((long)KW * cin * M)), dim3(256), 0, s, gi.A, gi.xs_b, gi.xs_t, B,
-                           T, cin, KW, pad, TBUF, M);
-        tr_gemm(KW * cin, C, (int)M, TBUF, M, c->DZb.as<float>(), C, gvar(c, sc + "conv1d/kernel"), C, s);
+        tr_im2col_t(gi.A, gi.xs_b, gi.xs_t, B, T, cin, KW, pad, TBUF, M, s);
+        tr_gemm(c, KW * cin, C, (int)M, TBUF, M, c->DZb.as<float>(), C, gvar(c, sc + "conv1d/kernel"), C, s);
       }
     }
-    hipLaunchKernelGGL(k_pn_flip, dim3(nblk((long)KW * cin * C)), dim3(256), 0, s, pvar(c, sc + "conv1d/kernel"), KW,
-                       cin, C, c->WFLIP.as<float>());
+    tr_conv_flip(pvar(c, sc + "conv1d/kernel"), KW, cin, C, c->WFLIP.as<float>(), s);
     if (planes) {  // input gradient: conv of the dz planes with the flipped kernel (pad KW-1-pad = pad)
       kc_transpose_bf16(c->WFLIP.as<float>(), KW * C, cin, cin, wt, KW * C, (cin + 255) / 256 * 256, s);
       conv_bf16_planes(pl, C, B, T, KW, wt, (long)KW * C, cin, nullptr, ACT_NONE, dxo, cin, s);
@@ -2994,7 +2811,7 @@ static void tr_postnet(tt2_train_ctx* c, const float* tg, const uint8_t* pnm, in
       g.a_mode = A_CONV1D; g.M = (int)M; g.N = cin; g.T = T; g.kw = KW; g.pad = KW - 1 - pad;
       g.A = c->DZb.as<float>(); g.C = C; g.xs_b = (long)T * C; g.xs_t = C; g.K = KW * C;
       g.Bw = c->WFLIP.as<float>(); g.ldb = cin; g.Cout = dxo; g.ldc = cin;
-      tr_gemm_run(g, s);
+      tr_gemm_run(c, g, s);
     }
     std::swap(dxn, dxo);
   }
@@ -3030,11 +2847,24 @@ __global__ void k_tr_rank1_add(float* __restrict__ Y, long ld, const float* __re
 // d W_loc from the cumulative alignments (k_tr_dwloc_cum) instead of the stored location features:
 // the forward then skips FALL (TT2_TR_DWLOC_CUM=0: FALL + k_tr_dwloc)
 static bool tr_dwloc_cum_ok(const tt2_train_ctx* c) {
-  static const bool env = [] {
-    const char* e = std::getenv("TT2_TR_DWLOC_CUM");
-    return !(e && e[0] == '0');
-  }();
-  return env && c->KW <= 31 && c->F <= 32 && c->A <= 128;
+  return c->sw.dwloc_cum && c->KW <= 31 && c->F <= 32 && c->A <= 128;
+}
+
+// Stage stamps of one step (diagnostic): n zeroed int64 slots for a launch to fill ...
+static long long* tr_stamps_begin(tt2_train_ctx* c, size_t n, hipStream_t s) {
+  c->tpStamps.reserve(sizeof(long long) * n);
+  TT2_HIP(hipMemsetAsync(c->tpStamps.p, 0, c->tpStamps.bytes, s));
+  return c->tpStamps.as<long long>();
+}
+// ... read back once the stream has passed the launch, and written raw to `file`
+static void tr_stamps_dump(tt2_train_ctx* c, size_t n, const std::string& file, hipStream_t s) {
+  std::vector<long long> h(n);
+  TT2_HIP(hipMemcpyAsync(h.data(), c->tpStamps.p, n * sizeof(long long), hipMemcpyDeviceToHost, s));
+  TT2_HIP(hipStreamSynchronize(s));
+  if (FILE* f = std::fopen(file.c_str(), "wb")) {
+    std::fwrite(h.data(), sizeof(long long), n, f);
+    std::fclose(f);
+  }
 }
 
 // Persistent forward (train_persist.hip): fork widths (H 1024, prenet 256, memory 1024, attention 128
@@ -3047,14 +2877,11 @@ static bool tr_persist_fits(const tt2_train_ctx* c, int Tin, bool free_run, bool
 
 static void tr_persist_forward(tt2_train_ctx* c, const TrAtt& at, const uint8_t* zm, int Tin, int T, hipStream_t s) {
   const size_t xb = 2ul * 64 * 1024 * sizeof(__bf16);  // two parities of [64][1024] bf16
-  auto grow = [](DevBuf& d, size_t n) {
-    if (d.bytes < n) d.alloc(n);
-  };
-  for (DevBuf* d : {&c->tpCX, &c->tpH1X, &c->tpZ1X, &c->tpH2X, &c->tpZ2X}) grow(*d, xb);
-  grow(c->tpEX, 2ul * 64 * 4 * TP_TMAX * sizeof(unsigned long long));
-  grow(c->tpCtl, sizeof(unsigned) * (3ul * TP_NREP * TP_NB + 16));
-  grow(c->tpPre, (size_t)T * 64 * TP_P * sizeof(__bf16));
-  grow(c->tpKWT, sizeof(float) * TP_A * 32);
+  for (DevBuf* d : {&c->tpCX, &c->tpH1X, &c->tpZ1X, &c->tpH2X, &c->tpZ2X}) d->reserve(xb);
+  c->tpEX.reserve(2ul * 64 * 4 * TP_TMAX * sizeof(unsigned long long));
+  c->tpCtl.reserve(sizeof(unsigned) * (3ul * TP_NREP * TP_NB + 16));
+  c->tpPre.reserve((size_t)T * 64 * TP_P * sizeof(__bf16));
+  c->tpKWT.reserve(sizeof(float) * TP_A * 32);
   if (!c->tp_ctl_host) TT2_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->tp_ctl_host), 4 * sizeof(int)));
   // rows >= B of the exchange buffers stay zero (they are A-operand padding); the flags and the
   // granules restart their tags at 1 every launch
@@ -3075,7 +2902,7 @@ static void tr_persist_forward(tt2_train_ctx* c, const TrAtt& at, const uint8_t*
   // the persistent backward's packed unit operands (train_persist.h TpArgs::BPK), when it will run
   a.BPK = nullptr;
   if (c->tb_on && Tin <= TB_TMAX) {
-    grow(c->tbPK, (size_t)T * TP_NB * 4 * TP_NT * 4 * sizeof(float));
+    c->tbPK.reserve((size_t)T * TP_NB * 4 * TP_NT * 4 * sizeof(float));
     a.BPK = c->tbPK.as<float>();
   }
   a.CX = c->tpCX.as<__bf16>(); a.H1X = c->tpH1X.as<__bf16>(); a.Z1X = c->tpZ1X.as<__bf16>();
@@ -3084,35 +2911,17 @@ static void tr_persist_forward(tt2_train_ctx* c, const TrAtt& at, const uint8_t*
   a.flags = c->tpCtl.as<unsigned>();
   a.ctl = reinterpret_cast<int*>(a.flags + 3 * TP_NREP * TP_NB);
   // TT2_TP_STAMP=<step>: stage stamps of that step -> TT2_TP_STAMP_FILE (int64 [256][32], diagnostic)
-  const char* st = std::getenv("TT2_TP_STAMP");
-  a.stamp_step = st ? std::atoi(st) : -1;
-  {  // TT2_TP_OC: placement of the forward's off-chain products (A/B; k_tr_persist)
-    const char* e = std::getenv("TT2_TP_OC");
-    a.oc_mode = e ? std::atoi(e) : 1;  // mode 1 measured 69.9 against 70.45 ms/step (mode 0)
-  }
-  a.stamps = nullptr;
-  if (st) {
-    grow(c->tpStamps, sizeof(long long) * TP_NB * 32);
-    TT2_HIP(hipMemsetAsync(c->tpStamps.p, 0, c->tpStamps.bytes, s));
-    a.stamps = c->tpStamps.as<long long>();
-  }
+  a.stamp_step = c->sw.tp_stamp;
+  a.oc_mode = c->sw.tp_oc;  // A/B (k_tr_persist); DESIGN §5.6j: mode 1 measured 69.9 against 70.45 ms/step (mode 0)
+  a.stamps = a.stamp_step >= 0 ? tr_stamps_begin(c, (size_t)TP_NB * 32, s) : nullptr;
   tp_launch(a, s);
   c->tp_ctl_dev = a.ctl;
   // TT2_TP_FORCE_FAIL=1 (test hook): mark this launch's control word as a timed-out hand-off in phase
   // 0, as a stalled launch would, to exercise the status word and the skipped update
-  if (const char* ff = std::getenv("TT2_TP_FORCE_FAIL"))
+  if (const char* ff = std::getenv("TT2_TP_FORCE_FAIL"))  // (per launch: the test flips it between two steps of one trainer)
     if (ff[0] == '1') TT2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.ctl), 1, 1, s));
   if (!tr_dwloc_cum_ok(c)) tp_location_features(at.CUM, at.Kc, at.bc, c->B, T, Tin, at.FALL, s);
-  if (st) {
-    std::vector<long long> h((size_t)TP_NB * 32);
-    TT2_HIP(hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    TT2_HIP(hipStreamSynchronize(s));
-    const char* fn = std::getenv("TT2_TP_STAMP_FILE");
-    if (FILE* f = std::fopen(fn ? fn : "tp_stamps.bin", "wb")) {
-      std::fwrite(h.data(), sizeof(long long), h.size(), f);
-      std::fclose(f);
-    }
-  }
+  if (a.stamps) tr_stamps_dump(c, (size_t)TP_NB * 32, c->sw.tp_stamp_file, s);
   TT2_HIP(hipMemcpyAsync(c->tp_ctl_host, a.ctl, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   c->tp_check = true;
 }
@@ -3145,18 +2954,15 @@ static void tr_persist_check(tt2_train_ctx* c) {
 static void tr_persist_backward(tt2_train_ctx* c, const TrAtt& at, const uint8_t* zm, int Tin, int T, int NT,
                                 hipStream_t s) {
   const int B = c->B;
-  auto grow = [](DevBuf& d, size_t n) {
-    if (d.bytes < n) d.alloc(n);
-  };
   const size_t xg = 2ul * 64 * 4 * TP_H * sizeof(__bf16);
-  grow(c->tbG1X, xg);
-  grow(c->tbG2X, xg);
-  grow(c->tbP1X, 2ul * TB_NKB * 64 * TB_NOUT * sizeof(float));
-  grow(c->tbP2X, 2ul * TB_NKB * 64 * TB_NOUT * sizeof(float));
-  grow(c->tbQX, 2ul * 64 * TP_A * sizeof(__bf16));
-  grow(c->tbW1F, (size_t)TP_NB * 4 * 16 * 64 * 8 * sizeof(__bf16));
-  grow(c->tpEX, 2ul * 64 * 4 * TP_TMAX * sizeof(unsigned long long));
-  grow(c->tbCtl, sizeof(unsigned) * ((size_t)TB_NPH * TP_NREP * TP_NB + 16));
+  c->tbG1X.reserve(xg);
+  c->tbG2X.reserve(xg);
+  c->tbP1X.reserve(2ul * TB_NKB * 64 * TB_NOUT * sizeof(float));
+  c->tbP2X.reserve(2ul * TB_NKB * 64 * TB_NOUT * sizeof(float));
+  c->tbQX.reserve(2ul * 64 * TP_A * sizeof(__bf16));
+  c->tbW1F.reserve((size_t)TP_NB * 4 * 16 * 64 * 8 * sizeof(__bf16));
+  c->tpEX.reserve(2ul * 64 * 4 * TP_TMAX * sizeof(unsigned long long));
+  c->tbCtl.reserve(sizeof(unsigned) * ((size_t)TB_NPH * TP_NREP * TP_NB + 16));
   if (!c->tp_ctl_host) TT2_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->tp_ctl_host), 4 * sizeof(int)));
   // rows >= B of the dG exchange rows stay zero (A-operand padding); tags restart at 1 every launch
   tr_zero_many({{c->tbG1X.p, c->tbG1X.bytes}, {c->tbG2X.p, c->tbG2X.bytes}, {c->tbQX.p, c->tbQX.bytes},
@@ -3180,11 +2986,10 @@ static void tr_persist_backward(tt2_train_ctx* c, const TrAtt& at, const uint8_t
     long np1, kp1, np2, kp2;
     gemm_bf16_kc_bt_dims(c->LX1, 4 * TP_H, T * B, &np1, &kp1);
     gemm_bf16_kc_bt_dims(2 * TP_H, 4 * TP_H, T * B, &np2, &kp2);
-    const char* e = std::getenv("TT2_TB_DGT");
-    if (B == 64 && c->blas_on && g_tr_prec == 2 && np1 == 4 * TP_H && np2 == 4 * TP_H && kp1 == (long)T * B &&
-        kp2 == kp1 && !(e && e[0] == '0')) {
-      grow(c->tbDGT1, (size_t)4 * TP_H * kp1 * sizeof(__bf16));
-      grow(c->tbDGT2, (size_t)4 * TP_H * kp1 * sizeof(__bf16));
+    if (B == 64 && c->sw.blas && tr_prec(c) == 2 && np1 == 4 * TP_H && np2 == 4 * TP_H && kp1 == (long)T * B &&
+        kp2 == kp1 && c->sw.tb_dgt) {
+      c->tbDGT1.reserve((size_t)4 * TP_H * kp1 * sizeof(__bf16));
+      c->tbDGT2.reserve((size_t)4 * TP_H * kp1 * sizeof(__bf16));
       a.DGT1 = c->tbDGT1.as<__bf16>();
       a.DGT2 = c->tbDGT2.as<__bf16>();
       a.dgt_ld = kp1;
@@ -3193,7 +2998,7 @@ static void tr_persist_backward(tt2_train_ctx* c, const TrAtt& at, const uint8_t
       long np3, kp3;
       gemm_bf16_kc_bt_dims(T * B, TP_P, 4 * TP_H, &np3, &kp3);
       if (kp3 == 4 * TP_H) {
-        grow(c->tbDGR1, (size_t)T * B * 4 * TP_H * sizeof(__bf16));
+        c->tbDGR1.reserve((size_t)T * B * 4 * TP_H * sizeof(__bf16));
         a.DGR1 = c->tbDGR1.as<__bf16>();
         c->tb_dgr = true;
       }
@@ -3207,26 +3012,11 @@ static void tr_persist_backward(tt2_train_ctx* c, const TrAtt& at, const uint8_t
   a.flags = c->tbCtl.as<unsigned>();
   a.ctl = reinterpret_cast<int*>(a.flags + (size_t)TB_NPH * TP_NREP * TP_NB);
   // TT2_TB_STAMP=<step>: stage stamps of that step -> TT2_TB_STAMP_FILE (int64 [256][32], diagnostic)
-  const char* st = std::getenv("TT2_TB_STAMP");
-  a.stamp_step = st ? std::atoi(st) : -1;
-  a.stamps = nullptr;
-  if (st) {
-    grow(c->tpStamps, sizeof(long long) * TP_NB * 32);
-    TT2_HIP(hipMemsetAsync(c->tpStamps.p, 0, c->tpStamps.bytes, s));
-    a.stamps = c->tpStamps.as<long long>();
-  }
+  a.stamp_step = c->sw.tb_stamp;
+  a.stamps = a.stamp_step >= 0 ? tr_stamps_begin(c, (size_t)TP_NB * 32, s) : nullptr;
   tb_launch(a, s);
   c->tb_ctl_dev = a.ctl;
-  if (st) {
-    std::vector<long long> h((size_t)TP_NB * 32);
-    TT2_HIP(hipMemcpyAsync(h.data(), a.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    TT2_HIP(hipStreamSynchronize(s));
-    const char* fn = std::getenv("TT2_TB_STAMP_FILE");
-    if (FILE* f = std::fopen(fn ? fn : "tb_stamps.bin", "wb")) {
-      std::fwrite(h.data(), sizeof(long long), h.size(), f);
-      std::fclose(f);
-    }
-  }
+  if (a.stamps) tr_stamps_dump(c, (size_t)TP_NB * 32, c->sw.tb_stamp_file, s);
   TT2_HIP(hipMemcpyAsync(c->tp_ctl_host + 2, a.ctl, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   c->tb_check = true;
 }
@@ -3260,9 +3050,6 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
   c->T_last = T;
   c->Tf_last = Tf;
   c->Tin_last = Tin;
-  g_tr_kpart = &c->kpart;
-  g_tr_prec = c->cfg.precision ? 2 : 0;
-  g_tr_ctx = c;
   // weight transposes for the backward products
   tr_transpose(pvar(c, L1V("kernel")), LX1, 4 * H, 4 * H, c->K1T.as<float>(), LX1, s);
   tr_transpose(pvar(c, L2V("kernel")), 2 * H, 4 * H, 4 * H, c->K2T.as<float>(), 2 * H, s);
@@ -3296,20 +3083,18 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
   hipLaunchKernelGGL(k_tr_inputs, dim3(nblk(TB * NM)), dim3(256), 0, s, tg, B, T, NM, R, c->XIN.as<float>());
   hipLaunchKernelGGL(k_tr_values, dim3(nblk((long)B * Tin * D)), dim3(256), 0, s, mem, lens, B, Tin, D,
                      c->values.as<float>());
-  tr_gemm(B * Tin, A, D, c->values.as<float>(), D, pvar(c, vn("memory_layer/kernel")), A, c->keys.as<float>(), A, s);
+  tr_gemm(c, B * Tin, A, D, c->values.as<float>(), D, pvar(c, vn("memory_layer/kernel")), A, c->keys.as<float>(), A, s);
   // prenet over all steps at once (teacher-forced inputs are known up front)
-  tr_gemm((int)TB, P, NM, c->XIN.as<float>(), NM, pvar(c, PRV(1, "kernel")), P, c->P1.as<float>(), P, s,
+  tr_gemm(c, (int)TB, P, NM, c->XIN.as<float>(), NM, pvar(c, PRV(1, "kernel")), P, c->P1.as<float>(), P, s,
           pvar(c, PRV(1, "bias")), nullptr, 0, ACT_RELU);
   hipLaunchKernelGGL(k_tr_prenet_mask, dim3(nblk(TB * P)), dim3(256), 0, s, c->P1.as<float>(), (long)P, pm, 0, T, B, P);
-  tr_gemm((int)TB, P, P, c->P1.as<float>(), P, pvar(c, PRV(2, "kernel")), P, X1, LX1, s, pvar(c, PRV(2, "bias")),
+  tr_gemm(c, (int)TB, P, P, c->P1.as<float>(), P, pvar(c, PRV(2, "kernel")), P, X1, LX1, s, pvar(c, PRV(2, "bias")),
           nullptr, 0, ACT_RELU);
   hipLaunchKernelGGL(k_tr_prenet_mask, dim3(nblk(TB * P)), dim3(256), 0, s, X1, (long)LX1, pm, 1, T, B, P);
   // fused per-step products (k_tr_fused: product + consumer epilogue in one launch, forward and
   // backward) on bf16 shadows of their input rows; TT2_TR_FUSED=0 keeps the split-K products +
   // combines (A/B)
-  const char* fe = std::getenv("TT2_TR_FUSED");
-  const bool fused_env = !(fe && fe[0] == '0');
-  const bool fused = fused_env && g_tr_prec == 2 && B <= 64 && H % 32 == 0 && LX1 % 128 == 0 && A % 128 == 0;
+  const bool fused = c->sw.fused && tr_prec(c) == 2 && B <= 64 && H % 32 == 0 && LX1 % 128 == 0 && A % 128 == 0;
   __bf16* X1h = fused ? c->X1h.as<__bf16>() : nullptr;
   __bf16* X2h = fused ? c->X2h.as<__bf16>() : nullptr;
   const long Bp = (B + 31) & ~31L;  // rows per step of the TF-layout shadows
@@ -3336,8 +3121,8 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
   at.B = B; at.Tin = Tin; at.T = T; at.A = A; at.F = F; at.KW = KW; at.D = D; at.H = H; at.P = P;
   at.lens = lens; at.keys = c->keys.as<float>(); at.values = c->values.as<float>(); at.Q = c->Q.as<float>();
   at.values16 = nullptr;
-  if (g_tr_prec == 2 && c->values16_on && (D & 3) == 0) {  // bf16 copy of this step's values (once per step)
-    if (c->values16.bytes < (size_t)B * Tin * D * 2) c->values16.alloc((size_t)B * Tin * D * 2);  // grow only
+  if (tr_prec(c) == 2 && c->sw.values16 && (D & 3) == 0) {  // bf16 copy of this step's values (once per step)
+    c->values16.reserve((size_t)B * Tin * D * 2);
     hipLaunchKernelGGL(k_tr_to_bf16, dim3(2048), dim3(256), 0, s, c->values.as<float>(), (long)B * Tin, (long)D, (long)D,
                        c->values16.as<__bf16>());
     TT2_HIP(hipGetLastError());
@@ -3358,16 +3143,13 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
   at.PQ = c->PQ.as<float>();
   at.smooth = c->cfg.smoothing ? 1 : 0;
   if (at.smooth) {
-    if (c->SS.bytes < sizeof(float) * (size_t)T * B) c->SS.alloc(sizeof(float) * (size_t)T * B);
+    c->SS.reserve(sizeof(float) * (size_t)T * B);
     at.SS = c->SS.as<float>();
   }
   const int NT = (Tin + TR_JT - 1) / TR_JT;
   at.nt = NT;
   const dim3 att_grid(NT, B);
-  static const bool tr_e2 = [] {  // TT2_TR_E2=0: the 1024-thread energy kernel (A/B)
-    const char* e = std::getenv("TT2_TR_E2");
-    return !(e && e[0] == '0');
-  }();
+  const bool tr_e2 = c->sw.e2;  // TT2_TR_E2=0: the 1024-thread energy kernel (A/B)
   const unsigned bh = nblk((long)B * H);
 
   // teacher-forcing draw (TacoTrainingHelper.next_inputs, helpers.py:122-133): a step fed its own
@@ -3384,13 +3166,13 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       float* xin = c->XIN.as<float>() + s1 * NM;
       float* p1 = c->P1.as<float>() + s1 * P;
       // the last of step t-1's r frames (outputs[:, -output_dim:], helpers.py:129)
-      tr_gemm(B, NM, H + D, PIN + (s1 - B) * (H + D), H + D, pvar(c, FPV("kernel")) + (R - 1) * NM, NR, xin, NM, s,
+      tr_gemm(c, B, NM, H + D, PIN + (s1 - B) * (H + D), H + D, pvar(c, FPV("kernel")) + (R - 1) * NM, NR, xin, NM, s,
               pvar(c, FPV("bias")) + (R - 1) * NM);
-      tr_gemm(B, P, NM, xin, NM, pvar(c, PRV(1, "kernel")), P, p1, P, s, pvar(c, PRV(1, "bias")), nullptr, 0,
+      tr_gemm(c, B, P, NM, xin, NM, pvar(c, PRV(1, "kernel")), P, p1, P, s, pvar(c, PRV(1, "bias")), nullptr, 0,
               ACT_RELU);
       hipLaunchKernelGGL(k_tr_prenet_mask, dim3(nblk((long)B * P)), dim3(256), 0, s, p1, (long)P,
                          pm + (long)t * 2 * B * P, 0, 1, B, P);
-      tr_gemm(B, P, P, p1, P, pvar(c, PRV(2, "kernel")), P, X1 + s1 * LX1, LX1, s, pvar(c, PRV(2, "bias")), nullptr,
+      tr_gemm(c, B, P, P, p1, P, pvar(c, PRV(2, "kernel")), P, X1 + s1 * LX1, LX1, s, pvar(c, PRV(2, "bias")), nullptr,
               0, ACT_RELU);
       hipLaunchKernelGGL(k_tr_prenet_mask, dim3(nblk((long)B * P)), dim3(256), 0, s, X1 + s1 * LX1, (long)LX1,
                          pm + (long)t * 2 * B * P, 1, 1, B, P);
@@ -3419,7 +3201,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       hipLaunchKernelGGL(k_tr_fused<TF_FWD>, dim3(2 * H / TLG_U), dim3(TLG_NT), 0, s, f2);
     } else {
       // LSTM-1: raw split-K product, combine + bias + cell + zoneout fused in k_tr_lstm_fwd
-      const int k1 = tr_gemm_raw(B, 4 * H, LX1, X1 + s1 * LX1, LX1, pvar(c, L1V("kernel")), 4 * H, s, &c->hK1T, LX1);
+      const int k1 = tr_gemm_raw(c, B, 4 * H, LX1, X1 + s1 * LX1, LX1, pvar(c, L1V("kernel")), 4 * H, s, &c->hK1T, LX1);
       TrLstmFwd l1{};
       l1.G = c->G1.as<float>() + s1 * 4 * H; l1.part = c->kpart.as<float>(); l1.ks = k1; l1.bias = pvar(c, L1V("bias"));
       l1.c_prev = c->C1.as<float>() + s1 * H; l1.hz_prev = X1 + s1 * LX1 + P + D; l1.ld_hz_prev = LX1;
@@ -3427,7 +3209,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       l1.cn = c->CN1.as<float>() + s1 * H; l1.c_out = c->C1.as<float>() + (s1 + B) * H;
       l1.h_out = X2 + s1 * 2 * H; l1.ld_h = 2 * H; l1.hz_out = X1 + (s1 + B) * LX1 + P + D; l1.ld_hz = LX1;
       hipLaunchKernelGGL(k_tr_lstm_fwd, dim3(bh), dim3(256), 0, s, l1);
-      const int k2 = tr_gemm_raw(B, 4 * H, 2 * H, X2 + s1 * 2 * H, 2 * H, pvar(c, L2V("kernel")), 4 * H, s, &c->hK2T,
+      const int k2 = tr_gemm_raw(c, B, 4 * H, 2 * H, X2 + s1 * 2 * H, 2 * H, pvar(c, L2V("kernel")), 4 * H, s, &c->hK2T,
                                  2 * H);
       TrLstmFwd l2{};
       l2.G = c->G2.as<float>() + s1 * 4 * H; l2.part = c->kpart.as<float>(); l2.ks = k2; l2.bias = pvar(c, L2V("bias"));
@@ -3439,20 +3221,20 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
     }
     at.t = t;
     if (A <= 128 && tr_e2) {  // query as raw split-K partials, combined inside the energy kernel
-      at.qks = tr_gemm_raw(B, A, H, PIN + s1 * (H + D), H + D, pvar(c, vn("decoder/query_layer/kernel")), A, s,
+      at.qks = tr_gemm_raw(c, B, A, H, PIN + s1 * (H + D), H + D, pvar(c, vn("decoder/query_layer/kernel")), A, s,
                            &c->hWqT, H);
       at.qpart = c->kpart.as<float>();
       hipLaunchKernelGGL(k_tr_att_energy2, att_grid, dim3(TR_E2T), 0, s, at);
       at.qpart = nullptr;
     } else {
-      tr_gemm(B, A, H, PIN + s1 * (H + D), H + D, pvar(c, vn("decoder/query_layer/kernel")), A,
+      tr_gemm(c, B, A, H, PIN + s1 * (H + D), H + D, pvar(c, vn("decoder/query_layer/kernel")), A,
               c->Q.as<float>() + s1 * A, A, s, nullptr, nullptr, 0, ACT_NONE, &c->hWqT, H);
       hipLaunchKernelGGL(k_tr_att_energy, att_grid, dim3(TR_AT), 0, s, at);
     }
     hipLaunchKernelGGL(k_tr_ctx, dim3((D + 63) / 64, B), dim3(256), sizeof(float) * Tin, s, at);
   }
-  tr_gemm((int)TB, NR, H + D, PIN, H + D, pvar(c, FPV("kernel")), NR, c->FR.as<float>(), NR, s, pvar(c, FPV("bias")));
-  tr_gemm((int)TB, R, H + D, PIN, H + D, pvar(c, SPV("kernel")), R, c->ST.as<float>(), R, s, pvar(c, SPV("bias")));
+  tr_gemm(c, (int)TB, NR, H + D, PIN, H + D, pvar(c, FPV("kernel")), NR, c->FR.as<float>(), NR, s, pvar(c, FPV("bias")));
+  tr_gemm(c, (int)TB, R, H + D, PIN, H + D, pvar(c, SPV("kernel")), R, c->ST.as<float>(), R, s, pvar(c, SPV("bias")));
   float* red = c->red.as<float>();
   const int* tlen = c->cfg.mask_decoder ? c->TLEN.as<int>() : nullptr;
   const long nmse = c->cfg.mask_decoder ? c->tlen_sum * NM : TB * NR;
@@ -3470,16 +3252,16 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
   float* dPIN = c->dPIN.as<float>();
   float* dX1 = c->dX1.as<float>();
   float* dX2 = c->dX2.as<float>();
-  tr_gemm((int)TB, H + D, NR, c->dFR.as<float>(), NR, c->WfT.as<float>(), H + D, dPIN, H + D, s);
+  tr_gemm(c, (int)TB, H + D, NR, c->dFR.as<float>(), NR, c->WfT.as<float>(), H + D, dPIN, H + D, s);
   // + dST·W_s^T: a rank-1 update, streamed (as a K = 1 GEMM with the residual it took 0.69 ms); rank r
   // for r > 1
   if (R > 1)
-    tr_gemm((int)TB, H + D, R, c->dST.as<float>(), R, c->WsT.as<float>(), H + D, dPIN, H + D, s, nullptr, dPIN, H + D);
+    tr_gemm(c, (int)TB, H + D, R, c->dST.as<float>(), R, c->WsT.as<float>(), H + D, dPIN, H + D, s, nullptr, dPIN, H + D);
   else if ((H + D) % 4 == 0)
     hipLaunchKernelGGL(k_tr_rank1_add, dim3(2048), dim3(256), 0, s, dPIN, (long)(H + D), c->dST.as<float>(),
                        c->WsT.as<float>(), TB, H + D);
   else
-    tr_gemm((int)TB, H + D, 1, c->dST.as<float>(), 1, c->WsT.as<float>(), H + D, dPIN, H + D, s, nullptr, dPIN, H + D);
+    tr_gemm(c, (int)TB, H + D, 1, c->dST.as<float>(), 1, c->WsT.as<float>(), H + D, dPIN, H + D, s, nullptr, dPIN, H + D);
   tr_zero_many({{dX1 + TB * LX1, sizeof(float) * (size_t)B * LX1}, {dX2 + TB * 2 * H, sizeof(float) * (size_t)B * 2 * H},
                 {c->DC1.p, c->DC1.bytes}, {c->DC2.p, c->DC2.bytes}, {c->R1.p, c->R1.bytes}, {c->R2.p, c->R2.bytes},
                 {c->DKEYS.p, c->DKEYS.bytes}, {c->DCUM.p, c->DCUM.bytes}, {c->dV.p, c->dV.bytes}, {c->dBA.p, c->dBA.bytes},
@@ -3487,24 +3269,14 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
                s);
   // the attention backward as one launch of nq work-groups per row (k_tr_att_bwd_q; TT2_TR_ATTQ=0: the
   // two per-tile launches)
-  static const bool att_q_env = [] {
-    const char* e = std::getenv("TT2_TR_ATTQ");
-    return !(e && e[0] == '0');
-  }();
-  const bool att_q = att_q_env && fused && A == 128 && F == 32 && KW == 31 && D % 4 == 0 && D <= 1024 && Tin <= 256;
+  const bool att_q = c->sw.attq && fused && A == 128 && F == 32 && KW == 31 && D % 4 == 0 && D <= 1024 && Tin <= 256;
   const int nq = std::min(4, NT);
   if (att_q)
     for (DevBuf* d : {&c->DF2, &c->DCUM2, &c->SC2, &c->DWGP}) TT2_HIP(hipMemsetAsync(d->p, 0, d->bytes, s));
   at.DWGP = c->DWGP.as<float>();
   // TT2_ATTQ_STAMP=<step>: k_tr_att_bwd_q stage stamps of that step -> TT2_ATTQ_STAMP_FILE (diagnostic)
-  const char* aqs = std::getenv("TT2_ATTQ_STAMP");
-  at.stamps = nullptr;
-  at.stamp_t = aqs ? std::atoi(aqs) : -1;
-  if (aqs && att_q) {
-    if (c->tpStamps.bytes < sizeof(long long) * (size_t)B * 64) c->tpStamps.alloc(sizeof(long long) * (size_t)B * 64);
-    TT2_HIP(hipMemsetAsync(c->tpStamps.p, 0, c->tpStamps.bytes, s));
-    at.stamps = c->tpStamps.as<long long>();
-  }
+  at.stamp_t = c->sw.attq_stamp;
+  at.stamps = at.stamp_t >= 0 && att_q ? tr_stamps_begin(c, (size_t)B * 64, s) : nullptr;
   // the whole reverse loop as one persistent launch when the forward ran persistent (same geometry)
   const bool tb_run = c->tb_on && fused && Tin <= TB_TMAX && tr_persist_fits(c, Tin, free_run, at.values16 != nullptr);
   c->tb_last = tb_run;
@@ -3512,12 +3284,12 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
     tr_persist_backward(c, at, zm, Tin, T, NT, s);
     // the prenet columns of d X1 (off the recurrence): one product over all T·B rows (A = bf16(dG1) as the
     // launch wrote it, when it did)
-    if (c->tb_dgr && c->blas_on && g_tr_prec == 2) {
+    if (c->tb_dgr && c->sw.blas && tr_prec(c) == 2) {
       gemm_bf16_kc((int)TB, P, 4 * H, c->dG1.as<float>(), 4 * H, c->K1T.as<float>(), LX1, dX1, LX1, c->blasA, c->blasB,
                    c->blasP, s, false, nullptr, nullptr, c->tbDGR1.as<__bf16>());
       ++c->blas_calls;
     } else {
-      tr_gemm((int)TB, P, 4 * H, c->dG1.as<float>(), 4 * H, c->K1T.as<float>(), LX1, dX1, LX1, s);
+      tr_gemm(c, (int)TB, P, 4 * H, c->dG1.as<float>(), 4 * H, c->K1T.as<float>(), LX1, dX1, LX1, s);
     }
   }
   for (int t = tb_run ? -1 : T - 1; t >= 0; --t) {
@@ -3573,7 +3345,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       hipLaunchKernelGGL(k_tr_fused<TF_PLAIN>, dim3(2 * ((LX1 + 31) / 32)), dim3(TLG_NT), 0, s, f3);
     } else {
       // LSTM-2 backward: d h2 = DQ·Wq^T (raw split-K) + d PIN[t][:, :H], combined in the cell kernel
-      const int kq = tr_gemm_raw(B, H, A, c->DQ.as<float>() + s1 * A, A, c->WqT.as<float>(), H, s, &c->hWq, A);
+      const int kq = tr_gemm_raw(c, B, H, A, c->DQ.as<float>() + s1 * A, A, c->WqT.as<float>(), H, s, &c->hWq, A);
       TrLstmBwd b2{};
       b2.dh_ext = dPIN + s1 * (H + D); b2.ld_dh = H + D; b2.part = c->kpart.as<float>(); b2.ks = kq; b2.pN = H;
       b2.dhz = dX2 + (s1 + B) * 2 * H + H; b2.ld_dhz = 2 * H; b2.DC = c->DC2.as<float>();
@@ -3583,7 +3355,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       hipLaunchKernelGGL(k_tr_lstm_bwd, dim3(bh), dim3(256), 0, s, b2);
       // dX2 = dG2·K2^T + R2 (raw split-K): columns [0,H) are d h1_new (consumed by the LSTM-1
       // backward), columns [H,2H) = d hz2_{t-1} are written to dX2[t] by the same kernel
-      const int kx = tr_gemm_raw(B, 2 * H, 4 * H, c->dG2.as<float>() + s1 * 4 * H, 4 * H, c->K2T.as<float>(), 2 * H, s,
+      const int kx = tr_gemm_raw(c, B, 2 * H, 4 * H, c->dG2.as<float>() + s1 * 4 * H, 4 * H, c->K2T.as<float>(), 2 * H, s,
                                  &c->hK2, 4 * H);
       TrLstmBwd b1{};
       b1.dh_ext = nullptr; b1.ld_dh = 0; b1.part = c->kpart.as<float>(); b1.ks = kx; b1.pN = 2 * H;
@@ -3593,7 +3365,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       b1.zm = zm; b1.t = t; b1.layer = 0; b1.B = B; b1.H = H; b1.z = z;
       b1.dG = c->dG1.as<float>() + s1 * 4 * H; b1.R = c->R1.as<float>(); b1.ldr = LX1; b1.off_r = P + D;
       hipLaunchKernelGGL(k_tr_lstm_bwd, dim3(bh), dim3(256), 0, s, b1);
-      tr_gemm(B, LX1, 4 * H, c->dG1.as<float>() + s1 * 4 * H, 4 * H, c->K1T.as<float>(), LX1, dX1 + s1 * LX1, LX1, s,
+      tr_gemm(c, B, LX1, 4 * H, c->dG1.as<float>() + s1 * 4 * H, 4 * H, c->K1T.as<float>(), LX1, dX1 + s1 * LX1, LX1, s,
               nullptr, c->R1.as<float>(), LX1, ACT_NONE, &c->hK1, 4 * H);
     }
     if (free_run && t > 0 && !c->feed[t]) {
@@ -3605,58 +3377,48 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       float* dx = c->sDX.as<float>();
       hipLaunchKernelGGL(k_tr_prenet_bwd, dim3(nblk((long)B * P)), dim3(256), 0, s, dX1 + s1 * LX1, (long)LX1,
                          X1 + s1 * LX1, (long)LX1, (long)B, P, dz);
-      tr_gemm(B, P, P, dz, P, c->Wp2T.as<float>(), P, dp, P, s);
+      tr_gemm(c, B, P, P, dz, P, c->Wp2T.as<float>(), P, dp, P, s);
       hipLaunchKernelGGL(k_tr_prenet_bwd, dim3(nblk((long)B * P)), dim3(256), 0, s, dp, (long)P,
                          c->P1.as<float>() + s1 * P, (long)P, (long)B, P, dz);
-      tr_gemm(B, NM, P, dz, P, c->W1T.as<float>(), NM, dx, NM, s);
+      tr_gemm(c, B, NM, P, dz, P, c->W1T.as<float>(), NM, dx, NM, s);
       float* dfr = c->dFR.as<float>() + (s1 - B) * NR + (R - 1) * NM;  // the last of step t-1's r frames
-      tr_gemm(B, NM, P, dz, P, c->W1T.as<float>(), NM, dfr, NR, s, nullptr, dfr, NR);
+      tr_gemm(c, B, NM, P, dz, P, c->W1T.as<float>(), NM, dfr, NR, s, nullptr, dfr, NR);
       float* dpin = dPIN + (s1 - B) * (H + D);
-      tr_gemm(B, H + D, NM, dx, NM, c->WfT.as<float>() + (long)(R - 1) * NM * (H + D), H + D, dpin, H + D, s, nullptr,
+      tr_gemm(c, B, H + D, NM, dx, NM, c->WfT.as<float>() + (long)(R - 1) * NM * (H + D), H + D, dpin, H + D, s, nullptr,
               dpin, H + D);
     }
   }
 
   if (att_q && !tb_run)  // d query of step 0 (the later steps' sums were written by the launch after them)
     hipLaunchKernelGGL(k_tr_dq_sum, dim3(B), dim3(128), 0, s, c->PQ2.as<float>(), NT, nq, A, c->DQ.as<float>());
-  if (at.stamps) {
-    std::vector<long long> h((size_t)B * 64);
-    TT2_HIP(hipMemcpyAsync(h.data(), at.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    TT2_HIP(hipStreamSynchronize(s));
-    const char* fn = std::getenv("TT2_ATTQ_STAMP_FILE");
-    if (FILE* f = std::fopen(fn ? fn : "attq_stamps.bin", "wb")) {
-      std::fwrite(h.data(), sizeof(long long), h.size(), f);
-      std::fclose(f);
-    }
-    at.stamps = nullptr;
-  }
+  if (at.stamps) tr_stamps_dump(c, (size_t)B * 64, c->sw.attq_stamp_file, s);
   // ---- weight gradients over all T·B rows ----
   float* TBUF = c->TBUF.as<float>();
   const int TBi = (int)TB;
   const bool dgt = tb_run && c->tb_dgt;
-  tr_gemm_xtg(LX1, 4 * H, TBi, X1, LX1, c->dG1.as<float>(), 4 * H, gvar(c, L1V("kernel")), 4 * H, TBUF, s,
+  tr_gemm_xtg(c, LX1, 4 * H, TBi, X1, LX1, c->dG1.as<float>(), 4 * H, gvar(c, L1V("kernel")), 4 * H, TBUF, s,
               dgt ? c->tbDGT1.as<__bf16>() : nullptr);
   tr_colsum(c, c->dG1.as<float>(), TB, 4 * H, 4 * H, gvar(c, L1V("bias")), s);
-  tr_gemm_xtg(2 * H, 4 * H, TBi, X2, 2 * H, c->dG2.as<float>(), 4 * H, gvar(c, L2V("kernel")), 4 * H, TBUF, s,
+  tr_gemm_xtg(c, 2 * H, 4 * H, TBi, X2, 2 * H, c->dG2.as<float>(), 4 * H, gvar(c, L2V("kernel")), 4 * H, TBUF, s,
               dgt ? c->tbDGT2.as<__bf16>() : nullptr);
   tr_colsum(c, c->dG2.as<float>(), TB, 4 * H, 4 * H, gvar(c, L2V("bias")), s);
   tr_transpose(PIN, TB, H + D, H + D, TBUF, TB, s);
-  tr_gemm(H, A, TBi, TBUF, TB, c->DQ.as<float>(), A, gvar(c, vn("decoder/query_layer/kernel")), A, s);
-  tr_gemm(H + D, NR, TBi, TBUF, TB, c->dFR.as<float>(), NR, gvar(c, FPV("kernel")), NR, s);
-  tr_gemm(H + D, R, TBi, TBUF, TB, c->dST.as<float>(), R, gvar(c, SPV("kernel")), R, s);
+  tr_gemm(c, H, A, TBi, TBUF, TB, c->DQ.as<float>(), A, gvar(c, vn("decoder/query_layer/kernel")), A, s);
+  tr_gemm(c, H + D, NR, TBi, TBUF, TB, c->dFR.as<float>(), NR, gvar(c, FPV("kernel")), NR, s);
+  tr_gemm(c, H + D, R, TBi, TBUF, TB, c->dST.as<float>(), R, gvar(c, SPV("kernel")), R, s);
   tr_colsum(c, c->dFR.as<float>(), TB, NR, NR, gvar(c, FPV("bias")), s);
   tr_colsum(c, c->dST.as<float>(), TB, R, R, gvar(c, SPV("bias")), s);
   // prenet
   hipLaunchKernelGGL(k_tr_prenet_bwd, dim3(nblk(TB * P)), dim3(256), 0, s, dX1, (long)LX1, X1, (long)LX1, TB, P,
                      c->dZ.as<float>());
   tr_transpose(c->P1.as<float>(), TB, P, P, TBUF, TB, s);
-  tr_gemm(P, P, TBi, TBUF, TB, c->dZ.as<float>(), P, gvar(c, PRV(2, "kernel")), P, s);
+  tr_gemm(c, P, P, TBi, TBUF, TB, c->dZ.as<float>(), P, gvar(c, PRV(2, "kernel")), P, s);
   tr_colsum(c, c->dZ.as<float>(), TB, P, P, gvar(c, PRV(2, "bias")), s);
-  tr_gemm(TBi, P, P, c->dZ.as<float>(), P, c->Wp2T.as<float>(), P, c->dPre.as<float>(), P, s);
+  tr_gemm(c, TBi, P, P, c->dZ.as<float>(), P, c->Wp2T.as<float>(), P, c->dPre.as<float>(), P, s);
   hipLaunchKernelGGL(k_tr_prenet_bwd, dim3(nblk(TB * P)), dim3(256), 0, s, c->dPre.as<float>(), (long)P,
                      c->P1.as<float>(), (long)P, TB, P, c->dZ.as<float>());
   tr_transpose(c->XIN.as<float>(), TB, NM, NM, TBUF, TB, s);
-  tr_gemm(NM, P, TBi, TBUF, TB, c->dZ.as<float>(), P, gvar(c, PRV(1, "kernel")), P, s);
+  tr_gemm(c, NM, P, TBi, TBUF, TB, c->dZ.as<float>(), P, gvar(c, PRV(1, "kernel")), P, s);
   tr_colsum(c, c->dZ.as<float>(), TB, P, P, gvar(c, PRV(1, "bias")), s);
   // attention parameters: sums of the per-row partials
   const long BNT = (long)B * NT;
@@ -3698,7 +3460,7 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
       tr_colsum(c, TBUF, nbk, F * A, (long)F * A, gvar(c, LAV("location_features_layer/kernel")), s);
     } else {
       tr_transpose(c->FALL.as<float>(), R, F, F, TBUF, R, s);
-      tr_gemm(F, A, (int)R, TBUF, R, c->TH.as<float>(), A, gvar(c, LAV("location_features_layer/kernel")), A, s);
+      tr_gemm(c, F, A, (int)R, TBUF, R, c->TH.as<float>(), A, gvar(c, LAV("location_features_layer/kernel")), A, s);
     }
   }
   if (tb_run) {  // d Kc, d bc from the summed G (train_bwd_persist.h)
@@ -3716,14 +3478,11 @@ static void tr_forward_backward(tt2_train_ctx* c, const float* mem, const int* l
                      c->DCTX.as<float>(), B, Tin, T, D, c->DVAL.as<float>());
   TT2_HIP(hipGetLastError());
   tr_transpose(c->values.as<float>(), (long)B * Tin, D, D, TBUF, (long)B * Tin, s);
-  tr_gemm(D, A, B * Tin, TBUF, (long)B * Tin, c->DKEYS.as<float>(), A, gvar(c, vn("memory_layer/kernel")), A, s);
-  tr_gemm(B * Tin, D, A, c->DKEYS.as<float>(), A, c->WmT.as<float>(), D, c->DVAL.as<float>(), D, s, nullptr,
+  tr_gemm(c, D, A, B * Tin, TBUF, (long)B * Tin, c->DKEYS.as<float>(), A, gvar(c, vn("memory_layer/kernel")), A, s);
+  tr_gemm(c, B * Tin, D, A, c->DKEYS.as<float>(), A, c->WmT.as<float>(), D, c->DVAL.as<float>(), D, s, nullptr,
           c->DVAL.as<float>(), D);
   hipLaunchKernelGGL(k_tr_mask_rows, dim3(nblk((long)B * Tin * D)), dim3(256), 0, s, c->DVAL.as<float>(), lens, B, Tin,
                      D, c->DMEM.as<float>());
-  g_tr_kpart = nullptr;
-  g_tr_prec = 0;
-  g_tr_ctx = nullptr;
 }
 
 // L2 regularisation of the regularised kernels (after every gradient of the step has landed)
@@ -3741,825 +3500,6 @@ static void tr_regularize(tt2_train_ctx* c, hipStream_t s) {
                        c->reg_segs.as<long2>(), c->cfg.reg_weight, c->part.as<float>());
   hipLaunchKernelGGL(k_tr_sum_final, dim3(1), dim3(256), 0, s, c->part.as<float>(), 64 * c->nreg, c->cfg.reg_weight,
                      c->red.as<float>() + 2, 0);
-}
-
-// ---- front end (cfg.frontend): encoder, reference encoders, GST in training mode -------------------
-// The step starts from ids / reference mels: forward builds the memory the decoder slice consumes
-// (tacotron.py:215-308), backward continues from the decoder's d memory (DMEM) into every front-end
-// variable (train_front.hip kernels + gemm.hip products).
-static std::string fe_conv_scope(int i) {
-  return vn("encoder_convolutions/conv_layer_") + std::to_string(i) + "_encoder_convolutions/";
-}
-static std::string fe_ref_scope(const tt2_train_ctx* c, int r) {
-  return vn(c->f_adain ? "refnet/" : r == 0 ? "refnet_emt/" : "refnet_spk/");
-}
-// conv layer scope of stack r in conv2d_i/: AdaIN's two stacks share 'refnet/conv2d_i' and
-// tf.layers uniquifies the second (emotion) layer's default name (modules.py:84-87)
-static std::string fe_ref_conv(const tt2_train_ctx* c, int r) { return c->f_adain && r == 0 ? "conv2d_1/" : "conv2d/"; }
-// stride of refnet layer i: (2, 2) everywhere, AdaIN (2,2),(2,2),(1,1)x4 (tacotron.py:237)
-static int fe_ref_stride(const tt2_train_ctx* c, int i) { return c->f_adain && i >= 2 ? 1 : 2; }
-static std::string fe_mh_scope(int r) { return vn(r == 0 ? "Multihead-attention-emt/" : "Multihead-attention-spk/"); }
-static std::string fe_lstm_scope(int d) {
-  return vn(d == 0 ? "encoder_LSTM/bidirectional_rnn/fw/lstm_cell/" : "encoder_LSTM/bidirectional_rnn/bw/lstm_cell/");
-}
-static bool fe_regularized(const std::string& n) {  // tacotron.py:865-867 (oracle/train_ref.py regularized)
-  return !(n.find("bias") != std::string::npos || n.find("Bias") != std::string::npos ||
-           n.find("_projection") != std::string::npos || n.find("inputs_embedding") != std::string::npos ||
-           n.find("RNN") != std::string::npos || n.find("LSTM") != std::string::npos);
-}
-
-static void tr_front_build_vars(tt2_train_ctx* c, const std::function<void(const std::string&, std::vector<int64_t>, bool)>& add) {
-  const auto& f = c->cfg;
-  const int E = f.embedding_dim, C = f.enc_conv_channels, K = f.enc_conv_kernel, U = f.encoder_lstm_units;
-  auto addr = [&](const std::string& n, std::vector<int64_t> sh) { add(n, sh, fe_regularized(n)); };
-  addr(vn("inputs_embedding"), {f.n_symbols, E});
-  for (int i = 1; i <= f.enc_conv_layers; ++i) {
-    const std::string s = fe_conv_scope(i);
-    addr(s + "conv1d/kernel", {K, i == 1 ? E : C, C});
-    addr(s + "conv1d/bias", {C});
-    addr(s + "batch_normalization/gamma", {C});
-    addr(s + "batch_normalization/beta", {C});
-    add(s + "batch_normalization/moving_mean", {C}, false);
-    add(s + "batch_normalization/moving_variance", {C}, false);
-  }
-  for (int d = 0; d < 2; ++d) {
-    addr(fe_lstm_scope(d) + "kernel", {C + U, 4 * U});
-    addr(fe_lstm_scope(d) + "bias", {4 * U});
-  }
-  const int RD = f.reference_depth, tokd = f.style_embed_depth / f.num_heads, A = f.style_att_dim, dh = A / f.num_heads;
-  if (c->f_adain) {  // 'refnet' (modules.py:66-107): both conv stacks per layer, then GRU + dense
-    const std::string rs = fe_ref_scope(c, 1);
-    int ci = 1;
-    for (int i = 0; i < 6; ++i) {
-      const std::string s = rs + "conv2d_" + std::to_string(i) + "/";
-      for (int r = 1; r >= 0; --r) {  // speaker stack first (conv2d/), then emotion (conv2d_1/)
-        addr(s + fe_ref_conv(c, r) + "kernel", {3, 3, ci, f.reference_filters[i]});
-        addr(s + fe_ref_conv(c, r) + "bias", {f.reference_filters[i]});
-      }
-      ci = f.reference_filters[i];
-    }
-    addr(rs + "rnn/gru_cell/gates/kernel", {c->f_gin + RD, 2 * RD});
-    addr(rs + "rnn/gru_cell/gates/bias", {2 * RD});
-    addr(rs + "rnn/gru_cell/candidate/kernel", {c->f_gin + RD, RD});
-    addr(rs + "rnn/gru_cell/candidate/bias", {RD});
-    addr(rs + "dense/kernel", {RD, 128});
-    addr(rs + "dense/bias", {128});
-    return;
-  }
-  for (int r = 0; r < c->f_nref; ++r) {
-    const std::string rs = fe_ref_scope(c, r);
-    int ci = 1;
-    for (int i = 0; i < 6; ++i) {
-      const std::string s = rs + "conv2d_" + std::to_string(i) + "/";
-      addr(s + "conv2d/kernel", {3, 3, ci, f.reference_filters[i]});
-      addr(s + "conv2d/bias", {f.reference_filters[i]});
-      addr(s + "batch_normalization/gamma", {f.reference_filters[i]});
-      addr(s + "batch_normalization/beta", {f.reference_filters[i]});
-      add(s + "batch_normalization/moving_mean", {f.reference_filters[i]}, false);
-      add(s + "batch_normalization/moving_variance", {f.reference_filters[i]}, false);
-      ci = f.reference_filters[i];
-    }
-    addr(rs + "rnn/gru_cell/gates/kernel", {c->f_gin + RD, 2 * RD});
-    addr(rs + "rnn/gru_cell/gates/bias", {2 * RD});
-    addr(rs + "rnn/gru_cell/candidate/kernel", {c->f_gin + RD, RD});
-    addr(rs + "rnn/gru_cell/candidate/bias", {RD});
-    addr(rs + "dense/kernel", {RD, 128});
-    addr(rs + "dense/bias", {128});
-    if (!f.use_gst) continue;  // hp.use_gst = False: no style tokens / style attention (tacotron.py:284-291)
-    addr(vn(r == 0 ? "style_tokens_emt" : "style_tokens_spk"), {f.num_gst, tokd});
-    const std::string m = fe_mh_scope(r);
-    addr(m + "conv1d/kernel", {1, 128, A});
-    addr(m + "conv1d/bias", {A});
-    addr(m + "conv1d_1/kernel", {1, tokd, A});
-    addr(m + "conv1d_1/bias", {A});
-    addr(m + "attention_v", {dh});
-    addr(m + "attention_g", {});
-    addr(m + "attention_b", {dh});
-  }
-  // Style_Emb_Disc dense layers (modules.py:626-644, tacotron.py:489-493; oracle style_disc_var_names)
-  for (int r = 0; r < c->f_nref; ++r) {
-    const int n = r == 0 ? f.n_emt : f.n_spk;
-    if (n <= 0) continue;
-    const std::string sd = vn(r == 0 ? "style_disc_emt/dense/" : "style_disc_spk/dense/");
-    addr(sd + "kernel", {128, n});
-    addr(sd + "bias", {n});
-  }
-}
-
-// the encoder BiLSTM steps as fused products (k_tr_fused TF_EFWD / TF_EBWD): bf16 step, B <= 64,
-// U a multiple of 128; TT2_TR_FUSED=0 keeps the split products + cell launches
-static bool fe_enc_fused(tt2_train_ctx* c) {
-  const char* fe = std::getenv("TT2_TR_FUSED");
-  const int U = c->cfg.encoder_lstm_units;
-  return !(fe && fe[0] == '0') && g_tr_prec == 2 && c->B <= 64 && U % 128 == 0;
-}
-
-static void tr_front_alloc(tt2_train_ctx* c) {
-  const auto& f = c->cfg;
-  const long B = c->B, T = c->Tin, C = f.enc_conv_channels, E = f.embedding_dim, U = f.encoder_lstm_units;
-  const long BT = B * T, K = f.enc_conv_kernel;
-  auto a = [](DevBuf& d, long n) { d.alloc(sizeof(float) * (size_t)std::max<long>(n, 1)); };
-  a(c->fEX, BT * E);
-  const char* pe = std::getenv("TT2_PN_PLANES");  // 0: implicit-im2col gemm_x3_kernel convs here too
-  // one plane buffer serves the embedding (stride E) and the conv layers (stride C): the pad rows
-  // are zeroed once per shape, so the two strides must agree or the stride-E frames land on the
-  // stride-C pad rows (the im2col path serves E != C)
-  if ((!pe || std::atoi(pe) != 0) && c->cfg.precision && C % 64 == 0 && E == C && (K & 1) &&
-      K <= 2 * CX_P + 1) {
-    const long W = std::max(C, E), Wr = (W + 255) / 256 * 256;
-    c->fePl.alloc((size_t)cx_rows((int)B, (int)T) * W * 2);
-    c->feWt.alloc((size_t)Wr * K * W * 2);
-  }
-  for (int i = 0; i < f.enc_conv_layers; ++i) {
-    a(c->fEA[i], BT * C);
-    a(c->fEY[i + 1], BT * C);
-  }
-  a(c->fXP, BT * 8 * U); a(c->fGZ, 2 * B * 4 * U); a(c->fGA, 2 * T * B * 4 * U); a(c->fCN, 2 * T * B * U);
-  a(c->fCS, 2 * (T + 1) * B * U); a(c->fHS, 2 * (T + 1) * B * U); a(c->fENC, BT * 2 * U);
-  a(c->fMEM, BT * c->D); a(c->fSTY, B * (c->D - 2 * U)); a(c->fDSTY, B * (c->D - 2 * U));
-  a(c->fDZ, 2 * T * B * 4 * U); a(c->fDHC, 2 * B * U); a(c->fDCC, 2 * B * U); a(c->fDHP, 2 * B * U);
-  a(c->fdXP, BT * 8 * U); a(c->fdA, BT * std::max(C, E)); a(c->fdB, BT * std::max(C, E));
-  a(c->fLWxT, 2 * 4 * U * C); a(c->fLWhT, 2 * 4 * U * U);
-  {  // bf16 TF-layout operands of the fused encoder LSTM steps (k_tr_fused TF_EFWD / TF_EBWD)
-    const long Bp = (B + 31) & ~31L;
-    auto h = [](DevBuf& d, long n) { d.alloc(2 * (size_t)std::max<long>(n, 1)); };
-    h(c->fTWf, 2 * 4 * U * U); h(c->fTWb, 2 * 4 * U * U); h(c->fHSh, 2 * (T + 1) * Bp * U); h(c->fDZh, 2 * 2 * Bp * 4 * U);
-  }
-  // reference encoders at max_T_ref
-  const int RD = f.reference_depth, nm = c->NM;
-  long fbuf = BT * K * std::max(C, E);  // encoder im2col^T
-  // fDY / fDZc hold the refnet conv activations' gradients AND the encoder convs' BN backward
-  // (dy, dz: B·T_in·C each)
-  long mmax = BT * C;
-  long wt_conv2d = 1;  // largest 3x3 conv2d kernel transpose [fo][9·ci]
-  int H = f.max_T_ref, W = nm, ci = 1;
-  for (int i = 0; i < 6; ++i) {
-    const int st = fe_ref_stride(c, i), Ho = (H + st - 1) / st, Wo = (W + st - 1) / st, fo = f.reference_filters[i];
-    const long M = B * Ho * Wo;
-    for (int r = 0; r < c->f_nref; ++r) {
-      a(c->fRA[r][i], c->f_adain ? 1 : M * fo);  // pre-BN activations (AdaIN: no batch norm)
-      a(c->fRY[r][i], M * fo);
-    }
-    fbuf = std::max(fbuf, 9L * ci * M);
-    mmax = std::max(mmax, std::max(M * fo, B * (long)H * W * ci));
-    wt_conv2d = std::max(wt_conv2d, 9L * ci * fo);
-    H = Ho; W = Wo; ci = fo;
-  }
-  const long T2 = H;
-  c->f_T2max = (int)T2;
-  // FB also holds the transposes of the GRU states / inputs over all T2·B rows and the BiLSTM states
-  fbuf = std::max({fbuf, T2 * B * std::max<long>((long)W * ci, RD), BT * U, BT * C});
-  for (int r = 0; r < c->f_nref; ++r) {
-    a(c->fXG[r], B * T2 * 3 * RD); a(c->fGR[r], T2 * B * RD); a(c->fGU[r], T2 * B * RD); a(c->fGCC[r], T2 * B * RD);
-    a(c->fGRH[r], T2 * B * RD); a(c->fHG[r], (T2 + 1) * B * RD); a(c->fREF[r], B * 128);
-  }
-  a(c->fGG, B * 2 * RD); a(c->fGC, B * RD);
-  if (c->f_adain) {
-    const long nmap = T2 * B * (long)W * ci;
-    a(c->fADX, nmap); a(c->fDYE, std::max(mmax, nmap));
-    a(c->fADM, 2L * B * ci * 2); a(c->fADS, (long)B * ci * 2);
-    mmax = std::max(mmax, nmap);
-  }
-  a(c->fFBUF, fbuf); a(c->fDY, mmax); a(c->fDY2, mmax); a(c->fDZc, mmax);
-  // the direct conv2d kernel gradient sums its partial rows with tr_colsum over 9·ci·fo columns
-  if (c->part.bytes < sizeof(float) * (size_t)(wt_conv2d + 4096)) c->part.alloc(sizeof(float) * (size_t)(wt_conv2d + 4096));
-  const int ntok = f.num_gst, tokd = f.style_embed_depth / f.num_heads, A = f.style_att_dim, dh = A / f.num_heads;
-  a(c->fGq, B * A); a(c->fGkk, B * ntok * A); a(c->fGv, B * ntok * tokd); a(c->fGnv, B * dh); a(c->fGbb, B * dh);
-  a(c->fGsum, ntok * A + ntok * tokd + 2 * dh);
-  a(c->sXREF, 2 * B * 128); a(c->sDL, B * std::max(1, std::max(f.n_emt, f.n_spk))); a(c->sOM, B * B);
-  c->sLAB.alloc(sizeof(int) * (size_t)(2 * B));
-  a(c->fdREF, B * 128); a(c->fDZD, B * 128); a(c->fDH, B * RD); a(c->fDHA, B * RD); a(c->fDRH, B * RD);
-  a(c->fDCP, T2 * B * RD); a(c->fDGP, T2 * B * 2 * RD); a(c->fDXG, B * T2 * 3 * RD);
-  // transposed / flipped weight scratch: refnet conv2d kernels, GRU gates + candidate, dense, GST
-  // query, and the encoder conv flip K·cin·C with cin = E for the first layer
-  a(c->fWT, std::max<long>({wt_conv2d, 3L * RD * std::max<long>(c->f_gin, RD), 128L * RD, 128L * A,
-                            (long)K * std::max(C, E) * C}));
-  a(c->fBN, 2L * (f.enc_conv_layers + 6 * c->f_nref) * 512);
-  a(c->fpart, 64L * 2 * 512 + 1024);
-}
-
-// batch statistics over M rows of [M][C] into mean / var (k_pn_colstat: biased variance)
-static void fe_stats(tt2_train_ctx* c, const float* x, long M, int C, float* mean, float* var, hipStream_t s) {
-  const int S = tr_splits(M, C, 64L * 512);
-  const unsigned CT = (unsigned)((C + tr_tw(C) - 1) / tr_tw(C));
-  float* part = c->fpart.as<float>();
-  hipLaunchKernelGGL(k_pn_colstat_part, dim3(CT, S), dim3(256), 0, s, x, M, C, nullptr, 0, part);
-  hipLaunchKernelGGL(k_pn_colstat_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, 1.0f / (float)M, mean);
-  hipLaunchKernelGGL(k_pn_colstat_part, dim3(CT, S), dim3(256), 0, s, x, M, C, mean, 1, part);
-  hipLaunchKernelGGL(k_pn_colstat_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, 1.0f / (float)M, var);
-}
-// BN backward (batch statistics) from dy -> dz (act: 0 none, 2 relu' from the pre-BN activation)
-static void fe_bn_bwd(tt2_train_ctx* c, const float* dxn, const uint8_t* keep, const float* a, long M, int C,
-                      const float* mean, const float* var, const std::string& sc, int act, float* dy, float* dz,
-                      hipStream_t s, __bf16* planes = nullptr, int T = 1) {
-  const int S = tr_splits(M, C, 64L * 512);
-  float* part = c->fpart.as<float>();
-  float* sums = part + 64L * 2 * 512;
-  const float eps = c->cfg.bn_eps;
-  hipLaunchKernelGGL(k_pn_bn_bwd_part, dim3((unsigned)((C + tr_tw(C) - 1) / tr_tw(C)), S), dim3(256), 0, s, dxn, keep,
-                     a, M, C, mean, var, eps, dy, part);
-  hipLaunchKernelGGL(k_pn_bn_bwd_final, dim3((C + 31) / 32), dim3(TR_FIN), 0, s, part, S, C, sums,
-                     gvar(c, sc + "batch_normalization/gamma"), gvar(c, sc + "batch_normalization/beta"));
-  hipLaunchKernelGGL(k_pn_bn_bwd_dz, dim3(nblk(M * C)), dim3(256), 0, s, dy, a, M, C, mean, var, eps,
-                     pvar(c, sc + "batch_normalization/gamma"), sums, act, dz, planes, T);
-}
-
-// fp32 rows [B·T][C] (batch-major) -> the padded bf16 planes of conv_bf16_planes (frame rows only)
-__global__ void k_rows_to_planes(const float* __restrict__ x, long M, int C, int T, __bf16* __restrict__ planes) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < M * C) pn_plane_put(planes, T, i, C, x[i]);
-}
-
-static FeGst fe_gst_args(tt2_train_ctx* c, int r, int B) {
-  const auto& f = c->cfg;
-  const std::string m = fe_mh_scope(r);
-  FeGst g{};
-  g.ref = c->fREF[r].as<float>();
-  g.tokens = pvar(c, vn(r == 0 ? "style_tokens_emt" : "style_tokens_spk"));
-  g.wq = pvar(c, m + "conv1d/kernel"); g.bq = pvar(c, m + "conv1d/bias");
-  g.wk = pvar(c, m + "conv1d_1/kernel"); g.bk = pvar(c, m + "conv1d_1/bias");
-  g.v = pvar(c, m + "attention_v"); g.g = pvar(c, m + "attention_g"); g.bb = pvar(c, m + "attention_b");
-  g.N = B; g.ntok = f.num_gst; g.tokd = f.style_embed_depth / f.num_heads; g.A = f.style_att_dim; g.heads = f.num_heads;
-  g.refd = 128;
-  g.style = c->fSTY.as<float>(); g.style_ld = c->D - 2 * f.encoder_lstm_units; g.style_off = r * f.style_embed_depth;
-  g.dstyle = c->fDSTY.as<float>();
-  g.dq = c->fGq.as<float>(); g.pdkk = c->fGkk.as<float>(); g.pdv = c->fGv.as<float>(); g.pdnv = c->fGnv.as<float>();
-  g.pdbb = c->fGbb.as<float>();
-  return g;
-}
-
-static void tr_front_forward(tt2_train_ctx* c, const int* ids, const int* lens, const float* const* refs, int T_ref,
-                             const uint8_t* encm, const uint8_t* enczm, int T, hipStream_t s) {
-  const auto& f = c->cfg;
-  const int B = c->B, E = f.embedding_dim, C = f.enc_conv_channels, K = f.enc_conv_kernel, U = f.encoder_lstm_units;
-  const long M = (long)B * T;
-  const float eps = f.bn_eps;
-  float* BN = c->fBN.as<float>();
-  fe_embed(ids, pvar(c, vn("inputs_embedding")), M, E, c->fEX.as<float>(), s);
-  // EncoderConvolutions (modules.py:251-280, conv1d() :485-497 with bnorm 'after'): conv -> ReLU ->
-  // BN (batch statistics over all B·T positions) -> dropout(0.5, keep bits)
-  // bf16 conv over padded planes (conv_bf16_planes, as the Postnet's): planes of the embedding here,
-  // of each layer's output from its BN forward; pad rows zeroed once per shape
-  const bool planes = c->fePl.p && g_tr_prec == 2;
-  __bf16* pl = reinterpret_cast<__bf16*>(c->fePl.p);
-  __bf16* wt = reinterpret_cast<__bf16*>(c->feWt.p);
-  if (planes) {
-    if (c->fe_pl_B != B || c->fe_pl_T != T) {
-      TT2_HIP(hipMemsetAsync(c->fePl.p, 0, c->fePl.bytes, s));
-      c->fe_pl_B = B;
-      c->fe_pl_T = T;
-    }
-    hipLaunchKernelGGL(k_rows_to_planes, dim3(nblk(M * E)), dim3(256), 0, s, c->fEX.as<float>(), M, E, T, pl);
-  }
-  for (int i = 0; i < f.enc_conv_layers; ++i) {
-    const std::string sc = fe_conv_scope(i + 1);
-    const int cin = i == 0 ? E : C;
-    if (planes) {
-      kc_transpose_bf16(pvar(c, sc + "conv1d/kernel"), K * cin, C, C, wt, K * cin, (C + 255) / 256 * 256, s);
-      conv_bf16_planes(pl, cin, B, T, K, wt, (long)K * cin, C, pvar(c, sc + "conv1d/bias"), ACT_RELU,
-                       c->fEA[i].as<float>(), C, s);
-    } else {
-      GemmArgs g;
-      g.a_mode = A_CONV1D; g.M = (int)M; g.N = C; g.T = T; g.kw = K; g.pad = (K - 1) / 2; g.C = cin;
-      g.A = i == 0 ? c->fEX.as<float>() : c->fEY[i].as<float>(); g.xs_b = (long)T * cin; g.xs_t = cin; g.K = K * cin;
-      g.Bw = pvar(c, sc + "conv1d/kernel"); g.ldb = C; g.Cout = c->fEA[i].as<float>(); g.ldc = C;
-      g.bias = pvar(c, sc + "conv1d/bias"); g.act = ACT_RELU;
-      tr_gemm_run(g, s);
-    }
-    float* mean = BN + (long)i * 2 * 512;
-    float* var = mean + 512;
-    fe_stats(c, c->fEA[i].as<float>(), M, C, mean, var, s);
-    hipLaunchKernelGGL(k_pn_bn_fwd, dim3(nblk(M * C)), dim3(256), 0, s, c->fEA[i].as<float>(), M, C, mean, var,
-                       pvar(c, sc + "batch_normalization/gamma"), pvar(c, sc + "batch_normalization/beta"), eps,
-                       encm ? encm + (long)i * M * C : nullptr, c->fEY[i + 1].as<float>(),
-                       planes && i + 1 < f.enc_conv_layers ? pl : nullptr, T);
-  }
-  // EncoderRNN (modules.py:283-323): input projections of both directions for every position
-  const float* X = c->fEY[f.enc_conv_layers].as<float>();
-  for (int d = 0; d < 2; ++d)
-    tr_gemm((int)M, 4 * U, C, X, C, pvar(c, fe_lstm_scope(d) + "kernel"), 4 * U, c->fXP.as<float>() + d * 4 * U, 8 * U,
-            s, pvar(c, fe_lstm_scope(d) + "bias"));
-  TT2_HIP(hipMemsetAsync(c->fENC.p, 0, sizeof(float) * (size_t)M * 2 * U, s));
-  for (int d = 0; d < 2; ++d) {  // zero initial states
-    TT2_HIP(hipMemsetAsync(c->fCS.as<float>() + (long)d * (T + 1) * B * U, 0, sizeof(float) * (size_t)B * U, s));
-    TT2_HIP(hipMemsetAsync(c->fHS.as<float>() + (long)d * (T + 1) * B * U, 0, sizeof(float) * (size_t)B * U, s));
-  }
-  FeLstm l{};
-  l.XP = c->fXP.as<float>(); l.GZ = c->fGZ.as<float>(); l.GA = c->fGA.as<float>(); l.CN = c->fCN.as<float>();
-  l.CS = c->fCS.as<float>(); l.HS = c->fHS.as<float>(); l.ENC = c->fENC.as<float>(); l.zm = enczm; l.lens = lens;
-  l.B = B; l.T = T; l.U = U; l.zo = f.zoneout;
-  if (fe_enc_fused(c)) {  // both directions' recurrent product + cell in one launch per step
-    const long Bp = (B + 31) & ~31L;
-    for (int d = 0; d < 2; ++d)
-      hipLaunchKernelGGL(k_tr_tf_weights_f32, dim3(1024), dim3(256), 0, s, pvar(c, fe_lstm_scope(d) + "kernel") + (long)C * 4 * U,
-                         (long)4 * U, 1, 4 * U, U, U / 8, (int)TF_EFWD, U, c->fTWf.as<__bf16>() + (long)d * 4 * U * U);
-    for (int d = 0; d < 2; ++d)  // zero initial h
-      TT2_HIP(hipMemsetAsync(c->fHSh.as<__bf16>() + (long)d * (T + 1) * Bp * U, 0, 2 * (size_t)Bp * U, s));
-    TrFused e{};
-    e.Wt = c->fTWf.as<__bf16>(); e.wdir = (long)4 * U * U; e.K = U; e.B = B; e.H = U; e.T = T; e.lens = lens;
-    e.zm = enczm; e.zo = f.zoneout; e.XP = c->fXP.as<float>(); e.GA = c->fGA.as<float>(); e.CN = c->fCN.as<float>();
-    e.CS = c->fCS.as<float>(); e.HS = c->fHS.as<float>(); e.ENC = c->fENC.as<float>(); e.HSh = c->fHSh.as<__bf16>();
-    e.adir = (T + 1) * Bp * U;
-    for (int t = 0; t < T; ++t) {
-      e.t = t;
-      hipLaunchKernelGGL(k_tr_fused<TF_EFWD>, dim3(2 * 2 * U / 8), dim3(TLG_NT), 0, s, e);
-    }
-  } else {
-    for (int t = 0; t < T; ++t) {
-      for (int d = 0; d < 2; ++d)
-        tr_gemm(B, 4 * U, U, c->fHS.as<float>() + ((long)d * (T + 1) + t) * B * U, U,
-                pvar(c, fe_lstm_scope(d) + "kernel") + (long)C * 4 * U, 4 * U, c->fGZ.as<float>() + (long)d * B * 4 * U,
-                4 * U, s);
-      l.t = t;
-      fe_lstm_cell(l, s);
-    }
-  }
-  // reference encoders (modules.py:9-64) + GST (tacotron.py:276-282)
-  const int RD = f.reference_depth;
-  int nbn = f.enc_conv_layers;
-  for (int r = 0; r < c->f_nref; ++r) {
-    const std::string rs = fe_ref_scope(c, r);
-    int H = T_ref, W = c->NM, ci = 1;
-    const float* x = refs[r];
-    for (int i = 0; i < 6; ++i) {
-      const std::string sc = rs + "conv2d_" + std::to_string(i) + "/";
-      const int st = fe_ref_stride(c, i);
-      const int fo = f.reference_filters[i], Ho = (H + st - 1) / st, Wo = (W + st - 1) / st;
-      GemmArgs g;
-      g.M = B * Ho * Wo; g.N = fo; g.K = 9 * ci; g.a_mode = A_CONV2D; g.A = x;
-      g.H = H; g.Wd = W; g.C = ci; g.Ho = Ho; g.Wo = Wo; g.kh = 3; g.kw2 = 3; g.sh = st; g.sw = st;
-      g.pt = std::max((Ho - 1) * st + 3 - H, 0) / 2; g.pl = std::max((Wo - 1) * st + 3 - W, 0) / 2;
-      g.Bw = pvar(c, sc + fe_ref_conv(c, r) + "kernel"); g.ldb = fo; g.ldc = fo;
-      g.bias = pvar(c, sc + fe_ref_conv(c, r) + "bias");
-      const bool small = c->fe_direct && fe_conv2d_fwd_small_ok(ci, fo);  // first layer: direct kernel
-      if (c->f_adain) {  // conv2d(..., batch_norm=False): conv + ReLU (modules.py:84-87)
-        g.Cout = c->fRY[r][i].as<float>();
-        g.act = ACT_RELU;
-        if (small)
-          fe_conv2d_fwd_small(x, g.Bw, g.bias, B, H, W, ci, Ho, Wo, fo, g.pt, g.pl, st, true, g.Cout, s, g_tr_prec == 2);
-        else
-          tr_gemm_run(g, s);
-      } else {
-        g.Cout = c->fRA[r][i].as<float>();
-        if (small)
-          fe_conv2d_fwd_small(x, g.Bw, g.bias, B, H, W, ci, Ho, Wo, fo, g.pt, g.pl, st, false, g.Cout, s, g_tr_prec == 2);
-        else
-          tr_gemm_run(g, s);
-        float* mean = BN + (long)nbn * 2 * 512;
-        float* var = mean + 512;
-        fe_stats(c, c->fRA[r][i].as<float>(), g.M, fo, mean, var, s);
-        fe_bn_relu_fwd(c->fRA[r][i].as<float>(), g.M, fo, mean, var, pvar(c, sc + "batch_normalization/gamma"),
-                       pvar(c, sc + "batch_normalization/beta"), eps, c->fRY[r][i].as<float>(), s);
-        ++nbn;
-      }
-      x = c->fRY[r][i].as<float>();
-      H = Ho; W = Wo; ci = fo;
-    }
-    const int T2 = H, gin = W * ci;
-    c->f_T2 = T2;
-    if (c->f_adain) {
-      // moments over (time, freq) per row and channel (modules.py:90-91); the speaker map (r = 1,
-      // after the emotion stack r = 0) restyled into fADX, which alone feeds the GRU (:94-104)
-      float* mv = c->fADM.as<float>() + (long)r * B * ci * 2;
-      fe_ad_moments(x, B, T2 * W, ci, mv, s);
-      if (r == 0) continue;
-      fe_ad_mix(x, B, T2 * W, ci, mv, c->fADM.as<float>(), c->fADX.as<float>(), s);
-      x = c->fADX.as<float>();
-    }
-    const float* kg = pvar(c, rs + "rnn/gru_cell/gates/kernel");
-    const float* kcn = pvar(c, rs + "rnn/gru_cell/candidate/kernel");
-    float* XG = c->fXG[r].as<float>();
-    tr_gemm(B * T2, 2 * RD, gin, x, gin, kg, 2 * RD, XG, 3 * RD, s, pvar(c, rs + "rnn/gru_cell/gates/bias"));
-    tr_gemm(B * T2, RD, gin, x, gin, kcn, RD, XG + 2 * RD, 3 * RD, s, pvar(c, rs + "rnn/gru_cell/candidate/bias"));
-    TT2_HIP(hipMemsetAsync(c->fHG[r].p, 0, sizeof(float) * (size_t)B * RD, s));
-    if (c->fe_gru_seq && fe_gru_seq_ok(B, RD))  // the whole recurrence in one work-group (fp32 MFMA)
-      fe_gru_fwd_seq(XG, kg + (long)gin * 2 * RD, kcn + (long)gin * RD, B, T2, RD, c->fGR[r].as<float>(), c->fGU[r].as<float>(),
-                     c->fGRH[r].as<float>(), c->fGCC[r].as<float>(), c->fHG[r].as<float>(), s, g_tr_prec == 2);
-    for (int t = 0; t < (c->fe_gru_seq && fe_gru_seq_ok(B, RD) ? 0 : T2); ++t) {
-      float* h = c->fHG[r].as<float>() + (long)t * B * RD;
-      tr_gemm(B, 2 * RD, RD, h, RD, kg + (long)gin * 2 * RD, 2 * RD, c->fGG.as<float>(), 2 * RD, s);
-      fe_gru_a(XG, c->fGG.as<float>(), c->fHG[r].as<float>(), B, T2, RD, t, c->fGR[r].as<float>(),
-               c->fGU[r].as<float>(), c->fGRH[r].as<float>(), s);
-      tr_gemm(B, RD, RD, c->fGRH[r].as<float>() + (long)t * B * RD, RD, kcn + (long)gin * RD, RD, c->fGC.as<float>(), RD,
-              s);
-      fe_gru_b(XG, c->fGC.as<float>(), c->fGU[r].as<float>(), B, T2, RD, t, c->fGCC[r].as<float>(),
-               c->fHG[r].as<float>(), s);
-    }
-    tr_gemm(B, 128, RD, c->fHG[r].as<float>() + (long)T2 * B * RD, RD, pvar(c, rs + "dense/kernel"), 128,
-            c->fREF[r].as<float>(), 128, s, pvar(c, rs + "dense/bias"), nullptr, 0, ACT_TANH);
-    if (c->f_adain) {  // the speaker reference embedding is the style embedding (tacotron.py:269-272)
-      hipLaunchKernelGGL(k_tr_rows_copy, dim3(nblk((long)B * 128)), dim3(256), 0, s, c->fREF[r].as<float>(), 128L,
-                         (long)B, 128, c->fSTY.as<float>(), (long)(c->D - 2 * f.encoder_lstm_units),
-                         (const float*)nullptr, 0L);
-    } else if (f.use_gst) {
-      fe_gst_fwd(fe_gst_args(c, r, B), s);
-    } else {  // the reference embedding is the style embedding (tacotron.py:284-291)
-      const int SW = c->D - 2 * f.encoder_lstm_units;
-      hipLaunchKernelGGL(k_tr_rows_copy, dim3(nblk((long)B * 128)), dim3(256), 0, s, c->fREF[r].as<float>(), 128L,
-                         (long)B, 128, c->fSTY.as<float>() + r * 128, (long)SW, (const float*)nullptr, 0L);
-    }
-  }
-  fe_memory(c->fENC.as<float>(), c->fSTY.as<float>(), B, T, 2 * U, c->D - 2 * U, c->fMEM.as<float>(), s);
-  c->f_ran = true;
-}
-
-// ---- style-embedding losses (tacotron.py:486-495, 812-820, 840-846; oracle style_emb_losses) ----------
-// Style_Emb_Disc: logits = ref·W + b [B, n]; softmax_cross_entropy_with_logits against tf.one_hot(label)
-// (out-of-range label: zero row -> loss 0, gradient 0), batch mean.  One work-group per row: the
-// row's loss -> part[b], d logits = (softmax·Σy - y) / B -> DL, d ref += DL·Wᵀ -> XR.
-__global__ __launch_bounds__(128) void k_fe_disc(const float* __restrict__ ref, const float* __restrict__ Wk,
-                                                 const float* __restrict__ bk, const int* __restrict__ lab, int B,
-                                                 int n, float* __restrict__ DL, float* __restrict__ XR,
-                                                 float* __restrict__ part) {
-  extern __shared__ float sd[];  // [128] ref row, [n] logits
-  const int b = blockIdx.x, k = threadIdx.x;
-  float* lg = sd + 128;
-  sd[k] = ref[(long)b * 128 + k];
-  __syncthreads();
-  for (int j = k; j < n; j += 128) {
-    float v = bk[j];
-    for (int i = 0; i < 128; ++i) v = fmaf(sd[i], Wk[(long)i * n + j], v);
-    lg[j] = v;
-  }
-  __syncthreads();
-  const int y = lab[b];
-  const bool hot = y >= 0 && y < n;
-  if (k == 0) {  // serial over n (small): max, log-sum-exp, loss
-    float mx = -INFINITY;
-    for (int j = 0; j < n; ++j) mx = fmaxf(mx, lg[j]);
-    double se = 0;
-    for (int j = 0; j < n; ++j) se += exp((double)(lg[j] - mx));
-    const float lse = mx + (float)log(se);
-    part[b] = hot ? lse - lg[y] : 0.f;
-    sd[128 + n] = lse;
-  }
-  __syncthreads();
-  const float lse = sd[128 + n];
-  for (int j = k; j < n; j += 128) {
-    const float d = hot ? (expf(lg[j] - lse) - (j == y ? 1.f : 0.f)) / (float)B : 0.f;
-    DL[(long)b * n + j] = d;
-    lg[j] = d;
-  }
-  __syncthreads();
-  float g = 0.f;
-  for (int j = 0; j < n; ++j) g = fmaf(lg[j], Wk[(long)k * n + j], g);
-  XR[(long)b * 128 + k] += g;
-}
-// d W[k][j] = Σ_b ref[b][k] DL[b][j], d b[j] = Σ_b DL[b][j] (written, not accumulated)
-__global__ void k_fe_disc_wgrad(const float* __restrict__ ref, const float* __restrict__ DL, int B, int n,
-                                float* __restrict__ dW, float* __restrict__ db) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 128 * n) {
-    const int k = i / n, j = i % n;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v = fmaf(ref[(long)b * 128 + k], DL[(long)b * n + j], v);
-    dW[i] = v;
-  } else if (i < 129 * n) {
-    const int j = i - 128 * n;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) v += DL[(long)b * n + j];
-    db[j] = v;
-  }
-}
-// orthogonality loss w·||E·Sᵀ||_F: M = E·Sᵀ [B][B] (row b per work-group), Σ M² partials
-__global__ __launch_bounds__(128) void k_fe_orthog_m(const float* __restrict__ E, const float* __restrict__ S, int B,
-                                                     float* __restrict__ M, float* __restrict__ part) {
-  __shared__ float e[128];
-  __shared__ float s4[4];
-  const int b = blockIdx.x, t = threadIdx.x;
-  e[t] = E[(long)b * 128 + t];
-  __syncthreads();
-  float sq = 0.f;
-  for (int jj = t; jj < B; jj += 128) {
-    float v = 0.f;
-    for (int i = 0; i < 128; ++i) v = fmaf(e[i], S[(long)jj * 128 + i], v);
-    M[(long)b * B + jj] = v;
-    sq += v * v;
-  }
-  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-  if ((t & 63) == 0) s4[t >> 6] = sq;
-  __syncthreads();
-  if (t == 0) part[b] = s4[0] + s4[1];
-}
-// loss = w·||M|| -> red[0]; d E = (w/||M||)·M·S -> XE, d S = (w/||M||)·Mᵀ·E -> XS (accumulated);
-// blocks [0, B) rows of d E, [B, 2B) rows of d S.  ||M|| = 0: TF's norm gradient is NaN there; 0 here.
-__global__ __launch_bounds__(128) void k_fe_orthog_g(const float* __restrict__ E, const float* __restrict__ S,
-                                                     const float* __restrict__ M, int B, float w,
-                                                     const float* __restrict__ n2, float* __restrict__ red,
-                                                     float* __restrict__ XE, float* __restrict__ XS) {
-  const int r = blockIdx.x, k = threadIdx.x;
-  const float nrm = sqrtf(n2[0]);
-  if (r == 0 && k == 0) red[0] = w * nrm;
-  const float coef = nrm > 0.f ? w / nrm : 0.f;
-  float g = 0.f;
-  if (r < B) {
-    for (int j = 0; j < B; ++j) g = fmaf(M[(long)r * B + j], S[(long)j * 128 + k], g);
-    XE[(long)r * 128 + k] += coef * g;
-  } else {
-    const int j = r - B;
-    for (int b = 0; b < B; ++b) g = fmaf(M[(long)b * B + j], E[(long)b * 128 + k], g);
-    XS[(long)j * 128 + k] += coef * g;
-  }
-}
-
-// The style-embedding losses' gradients into the refnet outputs (sXREF[r]) and the classifier
-// weights; losses -> red[5] (emt), red[6] (spk), red[7] (orthogonality).  Before the refnet backward.
-static void tr_style_losses(tt2_train_ctx* c, hipStream_t s) {
-  const auto& f = c->cfg;
-  const int B = c->B;
-  float* red = c->red.as<float>();
-  float* XR = c->sXREF.as<float>();
-  TT2_HIP(hipMemsetAsync(XR, 0, sizeof(float) * (size_t)2 * B * 128, s));
-  TT2_HIP(hipMemsetAsync(red + 5, 0, sizeof(float) * 3, s));
-  for (int r = 0; r < c->f_nref; ++r) {
-    const int n = r == 0 ? f.n_emt : f.n_spk;
-    if (n <= 0) continue;
-    const std::string sd = vn(r == 0 ? "style_disc_emt/dense/" : "style_disc_spk/dense/");
-    hipLaunchKernelGGL(k_fe_disc, dim3(B), dim3(128), sizeof(float) * (129 + n), s, c->fREF[r].as<float>(),
-                       pvar(c, sd + "kernel"), pvar(c, sd + "bias"), c->sLAB.as<int>() + r * B, B, n, c->sDL.as<float>(),
-                       XR + (long)r * B * 128, c->part.as<float>());
-    hipLaunchKernelGGL(k_tr_sum_final, dim3(1), dim3(256), 0, s, c->part.as<float>(), B, 1.0f / B, red + 5 + r, 0);
-    hipLaunchKernelGGL(k_fe_disc_wgrad, dim3((129 * n + 255) / 256), dim3(256), 0, s, c->fREF[r].as<float>(),
-                       c->sDL.as<float>(), B, n, gvar(c, sd + "kernel"), gvar(c, sd + "bias"));
-  }
-  if (f.orthog_weight > 0.f && c->f_nref == 2) {
-    hipLaunchKernelGGL(k_fe_orthog_m, dim3(B), dim3(128), 0, s, c->fREF[0].as<float>(), c->fREF[1].as<float>(), B,
-                       c->sOM.as<float>(), c->part.as<float>());
-    hipLaunchKernelGGL(k_tr_sum_final, dim3(1), dim3(256), 0, s, c->part.as<float>(), B, 1.0f, red + 8, 0);
-    hipLaunchKernelGGL(k_fe_orthog_g, dim3(2 * B), dim3(128), 0, s, c->fREF[0].as<float>(), c->fREF[1].as<float>(),
-                       c->sOM.as<float>(), B, f.orthog_weight, red + 8, red + 7, XR, XR + (long)B * 128);
-  }
-  TT2_HIP(hipGetLastError());
-}
-
-static bool tr_style_on(const tt2_train_ctx* c) {
-  return c->cfg.n_emt > 0 || (c->f_nref == 2 && (c->cfg.n_spk > 0 || c->cfg.orthog_weight > 0.f));
-}
-
-static void tr_front_backward(tt2_train_ctx* c, const int* ids, const int* lens, const float* const* refs, int T_ref,
-                              const uint8_t* encm, const uint8_t* enczm, int T, hipStream_t s) {
-  const auto& f = c->cfg;
-  const int B = c->B, E = f.embedding_dim, C = f.enc_conv_channels, K = f.enc_conv_kernel, U = f.encoder_lstm_units;
-  const int D = c->D, RD = f.reference_depth, SW = D - 2 * U;
-  const long M = (long)B * T;
-  float* BN = c->fBN.as<float>();
-  float* WT = c->fWT.as<float>();
-  float* FB = c->fFBUF.as<float>();
-  // memory assembly: style gradient = Σ_t over the (length-masked) d memory rows
-  fe_style_grad(c->DMEM.as<float>(), B, T, D, 2 * U, c->fDSTY.as<float>(), s);
-  const bool style_on = tr_style_on(c);
-  if (style_on) tr_style_losses(c, s);
-  // conv2d stack r backward from d map `din` (conv -> BN -> ReLU per layer; AdaIN: conv -> ReLU)
-  const bool fe_direct = c->fe_direct;
-  auto conv_bwd = [&](int r, const float* din) {
-    const std::string rs = fe_ref_scope(c, r);
-    float* dY = c->fDY.as<float>();
-    int dims[7][3];
-    {
-      int H = T_ref, W = c->NM, ci = 1;
-      for (int i = 0; i < 6; ++i) {
-        dims[i][0] = H; dims[i][1] = W; dims[i][2] = ci;
-        const int st = fe_ref_stride(c, i);
-        H = (H + st - 1) / st; W = (W + st - 1) / st; ci = f.reference_filters[i];
-      }
-      dims[6][0] = H; dims[6][1] = W; dims[6][2] = ci;
-    }
-    for (int i = 5; i >= 0; --i) {
-      const int nbn = f.enc_conv_layers + 6 * r + i;  // forward order: encoder convs, then refnet r's layers
-      const std::string sc = rs + "conv2d_" + std::to_string(i) + "/", ly = fe_ref_conv(c, r);
-      const int H = dims[i][0], W = dims[i][1], ci = dims[i][2], Ho = dims[i + 1][0], Wo = dims[i + 1][1];
-      const int fo = f.reference_filters[i], st = fe_ref_stride(c, i);
-      const long Mi = (long)B * Ho * Wo;
-      float* dYr = c->fDY2.as<float>();
-      fe_relu_mask(i == 5 ? din : dY, c->fRY[r][i].as<float>(), Mi * fo, dYr, s);
-      float* dz = dYr;
-      if (!c->f_adain) {
-        const float* mean = BN + (long)nbn * 2 * 512;
-        const float* var = mean + 512;
-        dz = c->fDZc.as<float>();
-        fe_bn_bwd(c, dYr, nullptr, c->fRA[r][i].as<float>(), Mi, fo, mean, var, sc, 0, dYr, dz, s);
-      }
-      tr_colsum(c, dz, Mi, fo, fo, gvar(c, sc + ly + "bias"), s);
-      const int pt = std::max((Ho - 1) * st + 3 - H, 0) / 2, pl = std::max((Wo - 1) * st + 3 - W, 0) / 2;
-      const float* xin = i == 0 ? refs[r] : c->fRY[r][i - 1].as<float>();
-      // kernel gradient: direct (k_fe_conv2d_dw: patches staged in LDS, fp32 FMA, partial rows summed
-      // by tr_colsum) where its register / LDS budget takes the channel counts, else the im2colᵀ
-      // columns + GEMM (gemm_bf16_kc with the im2colᵀ gathered into bf16 measured 458 us per layer
-      // against 525 + ~60 for the fp32 columns + gemm_x3_kernel: its 256-wide N tile is 8x idle at fo = 32)
-      if (fe_direct && fe_conv2d_dw_ok(ci, fo)) {
-        const int rows = fe_conv2d_dw(xin, dz, B, H, W, ci, Ho, Wo, fo, pt, pl, st, FB, (long)(c->fFBUF.bytes / sizeof(float)),
-                                      s);
-        tr_colsum(c, FB, rows, 9 * ci * fo, 9L * ci * fo, gvar(c, sc + ly + "kernel"), s);
-      } else {
-        fe_im2col2d_t(xin, B, H, W, ci, Ho, Wo, pt, pl, FB, Mi, s, st);
-        tr_gemm(9 * ci, fo, (int)Mi, FB, Mi, dz, fo, gvar(c, sc + ly + "kernel"), fo, s);
-      }
-      if (i > 0) {
-        if (fe_direct && fe_conv2d_dx_ok(ci, W, Ho, Wo, fo, st)) {  // input gradient as a gather over the taps (k_fe_conv2d_dx)
-          fe_conv2d_dx(dz, pvar(c, sc + ly + "kernel"), B, H, W, ci, Ho, Wo, fo, pt, pl, st, dY, s);
-        } else {
-          tr_transpose(pvar(c, sc + ly + "kernel"), 9L * ci, fo, fo, WT, 9L * ci, s);  // [fo][9ci]
-          tr_gemm((int)Mi, 9 * ci, fo, dz, fo, WT, 9 * ci, FB, 9 * ci, s);
-          fe_col2im2d(FB, B, H, W, ci, Ho, Wo, pt, pl, dY, s, st);
-        }
-      }
-    }
-  };
-  for (int r = c->f_adain ? 1 : 0; r < c->f_nref; ++r) {
-    const std::string rs = fe_ref_scope(c, r), m = fe_mh_scope(r);
-    if (!f.use_gst || c->f_adain) {  // d ref = d style slice (+ style-loss terms)
-      hipLaunchKernelGGL(k_tr_rows_copy, dim3(nblk((long)B * 128)), dim3(256), 0, s,
-                         c->fDSTY.as<float>() + (c->f_adain ? 0 : r * 128),
-                         (long)SW, (long)B, 128, c->fdREF.as<float>(), 128L,
-                         style_on ? (const float*)(c->sXREF.as<float>() + (long)r * B * 128) : (const float*)nullptr,
-                         128L);
-    } else {
-    const FeGst ga = fe_gst_args(c, r, B);
-    fe_gst_bwd(ga, s);
-    const int ntok = ga.ntok, tokd = ga.tokd, A = ga.A, dh = A / ga.heads;
-    float* sum = c->fGsum.as<float>();
-    tr_colsum(c, ga.pdkk, B, ntok * A, (long)ntok * A, sum, s);
-    tr_colsum(c, ga.pdv, B, ntok * tokd, (long)ntok * tokd, sum + ntok * A, s);
-    tr_colsum(c, ga.pdnv, B, dh, dh, sum + ntok * A + ntok * tokd, s);
-    tr_colsum(c, ga.pdbb, B, dh, dh, sum + ntok * A + ntok * tokd + dh, s);
-    fe_gst_final(ga, sum, sum + ntok * A, sum + ntok * A + ntok * tokd, sum + ntok * A + ntok * tokd + dh,
-                 gvar(c, m + "conv1d_1/kernel"), gvar(c, m + "conv1d_1/bias"),
-                 gvar(c, vn(r == 0 ? "style_tokens_emt" : "style_tokens_spk")), gvar(c, m + "attention_v"),
-                 gvar(c, m + "attention_g"), gvar(c, m + "attention_b"), s);
-    // query conv1d (1x1): d Wq = refᵀ dq, d bq, d ref = dq Wqᵀ
-    tr_transpose(c->fREF[r].as<float>(), B, 128, 128, WT, B, s);
-    tr_gemm(128, A, B, WT, B, ga.dq, A, gvar(c, m + "conv1d/kernel"), A, s);
-    tr_colsum(c, ga.dq, B, A, A, gvar(c, m + "conv1d/bias"), s);
-    tr_transpose(pvar(c, m + "conv1d/kernel"), 128, A, A, WT, 128, s);
-    tr_gemm(B, 128, A, ga.dq, A, WT, 128, c->fdREF.as<float>(), 128, s, nullptr,
-            style_on ? c->sXREF.as<float>() + (long)r * B * 128 : nullptr, 128);  // + style-loss terms
-    }
-    // dense tanh (modules.py:63)
-    fe_tanh_bwd(c->fdREF.as<float>(), c->fREF[r].as<float>(), (long)B * 128, c->fDZD.as<float>(), s);
-    const int T2 = c->f_T2;
-    const float* hT = c->fHG[r].as<float>() + (long)T2 * B * RD;
-    tr_transpose(hT, B, RD, RD, WT, B, s);
-    tr_gemm(RD, 128, B, WT, B, c->fDZD.as<float>(), 128, gvar(c, rs + "dense/kernel"), 128, s);
-    tr_colsum(c, c->fDZD.as<float>(), B, 128, 128, gvar(c, rs + "dense/bias"), s);
-    tr_transpose(pvar(c, rs + "dense/kernel"), RD, 128, 128, WT, RD, s);
-    tr_gemm(B, RD, 128, c->fDZD.as<float>(), 128, WT, RD, c->fDH.as<float>(), RD, s);
-    // GRU BPTT (TF1 GRUCell): recurrent weight transposes once
-    const int gin = c->f_gin;
-    const float* kg = pvar(c, rs + "rnn/gru_cell/gates/kernel");
-    const float* kcn = pvar(c, rs + "rnn/gru_cell/candidate/kernel");
-    float* WghT = WT;                       // [2RD][RD]
-    float* WchT = WT + 2L * RD * RD;        // [RD][RD]
-    const bool gseq = c->fe_gru_seq && fe_gru_seq_ok(B, RD);
-    if (gseq) {  // the whole reverse recurrence in one work-group (fp32 MFMA)
-      fe_gru_bwd_seq(kg + (long)gin * 2 * RD, kcn + (long)gin * RD, c->fGR[r].as<float>(), c->fGU[r].as<float>(),
-                     c->fGCC[r].as<float>(), c->fHG[r].as<float>(), B, T2, RD, c->fDH.as<float>(), c->fDCP.as<float>(),
-                     c->fDGP.as<float>(), s, g_tr_prec == 2);
-    } else {
-      tr_transpose(kg + (long)gin * 2 * RD, RD, 2 * RD, 2 * RD, WghT, RD, s);
-      tr_transpose(kcn + (long)gin * RD, RD, RD, RD, WchT, RD, s);
-    }
-    for (int t = gseq ? -1 : T2 - 1; t >= 0; --t) {
-      fe_gru_bwd_a(c->fDH.as<float>(), c->fGU[r].as<float>(), c->fGCC[r].as<float>(), c->fHG[r].as<float>(), B, RD, t,
-                   c->fDCP.as<float>(), c->fDHA.as<float>(), s);
-      tr_gemm(B, RD, RD, c->fDCP.as<float>() + (long)t * B * RD, RD, WchT, RD, c->fDRH.as<float>(), RD, s);
-      fe_gru_bwd_b(c->fDRH.as<float>(), c->fGR[r].as<float>(), c->fGU[r].as<float>(), c->fHG[r].as<float>(),
-                   c->fGCC[r].as<float>(), c->fDH.as<float>(), B, RD, t, c->fDGP.as<float>(), c->fDHA.as<float>(), s);
-      tr_gemm(B, RD, 2 * RD, c->fDGP.as<float>() + (long)t * B * 2 * RD, 2 * RD, WghT, RD, c->fDH.as<float>(), RD, s,
-              nullptr, c->fDHA.as<float>(), RD);
-    }
-    // recurrent weight gradients over all steps: d Wg_h = Σ h(t)ᵀ dGP(t), d Wc_h = Σ (r h)(t)ᵀ dCP(t)
-    const long R2 = (long)T2 * B;
-    tr_transpose(c->fHG[r].as<float>(), R2, RD, RD, FB, R2, s);
-    tr_gemm(RD, 2 * RD, (int)R2, FB, R2, c->fDGP.as<float>(), 2 * RD, gvar(c, rs + "rnn/gru_cell/gates/kernel") +
-            (long)gin * 2 * RD, 2 * RD, s);
-    tr_transpose(c->fGRH[r].as<float>(), R2, RD, RD, FB, R2, s);
-    tr_gemm(RD, RD, (int)R2, FB, R2, c->fDCP.as<float>(), RD, gvar(c, rs + "rnn/gru_cell/candidate/kernel") +
-            (long)gin * RD, RD, s);
-    // input side over all (n, t) rows: DXG = [dGP | dCP] in (n, t) order
-    fe_gru_dxg(c->fDGP.as<float>(), c->fDCP.as<float>(), B, T2, RD, c->fDXG.as<float>(), s);
-    const float* x6 = c->f_adain ? c->fADX.as<float>() : c->fRY[r][5].as<float>();
-    tr_transpose(x6, R2, gin, gin, FB, R2, s);
-    tr_gemm(gin, 2 * RD, (int)R2, FB, R2, c->fDXG.as<float>(), 3 * RD, gvar(c, rs + "rnn/gru_cell/gates/kernel"),
-            2 * RD, s);
-    tr_gemm(gin, RD, (int)R2, FB, R2, c->fDXG.as<float>() + 2 * RD, 3 * RD,
-            gvar(c, rs + "rnn/gru_cell/candidate/kernel"), RD, s);
-    tr_colsum(c, c->fDXG.as<float>(), R2, 2 * RD, 3 * RD, gvar(c, rs + "rnn/gru_cell/gates/bias"), s);
-    tr_colsum(c, c->fDXG.as<float>() + 2 * RD, R2, RD, 3 * RD, gvar(c, rs + "rnn/gru_cell/candidate/bias"), s);
-    float* dY = c->fDY.as<float>();
-    tr_transpose(kg, gin, 2 * RD, 2 * RD, WT, gin, s);  // [2RD][gin]
-    tr_gemm((int)R2, gin, 2 * RD, c->fDXG.as<float>(), 3 * RD, WT, gin, dY, gin, s);
-    tr_transpose(kcn, gin, RD, RD, WT, gin, s);
-    tr_gemm((int)R2, gin, RD, c->fDXG.as<float>() + 2 * RD, 3 * RD, WT, gin, dY, gin, s, nullptr, dY, gin);
-    if (!c->f_adain) {
-      conv_bwd(r, dY);
-      continue;
-    }
-    // AdaIN: the restyle's backward splits d map into the speaker map's gradient (in place) and the
-    // emotion map's (through its moments), then both stacks run backward
-    const int C6 = f.reference_filters[5], HW = T2 * (gin / C6);
-    fe_ad_mix_bwd(dY, c->fRY[1][5].as<float>(), c->fRY[0][5].as<float>(), B, HW, C6, c->fADM.as<float>() + (long)B * C6 * 2,
-                  c->fADM.as<float>(), c->fADS.as<float>(), dY, c->fDYE.as<float>(), s);
-    conv_bwd(1, dY);  // (din is read by the top layer's ReLU mask before any col2im writes dY)
-    conv_bwd(0, c->fDYE.as<float>());
-  }
-  // BiLSTM BPTT (the decoder's DMEM rows carry d enc_out in columns [0, 2U))
-  for (int d = 0; d < 2; ++d) {
-    const float* k = pvar(c, fe_lstm_scope(d) + "kernel");
-    tr_transpose(k + (long)C * 4 * U, U, 4 * U, 4 * U, c->fLWhT.as<float>() + (long)d * 4 * U * U, U, s);
-    tr_transpose(k, C, 4 * U, 4 * U, c->fLWxT.as<float>() + (long)d * 4 * U * C, C, s);
-  }
-  TT2_HIP(hipMemsetAsync(c->fDHC.p, 0, c->fDHC.bytes, s));
-  TT2_HIP(hipMemsetAsync(c->fDCC.p, 0, c->fDCC.bytes, s));
-  FeLstm l{};
-  l.GA = c->fGA.as<float>(); l.CN = c->fCN.as<float>(); l.CS = c->fCS.as<float>(); l.HS = c->fHS.as<float>();
-  l.zm = enczm; l.lens = lens; l.B = B; l.T = T; l.U = U; l.zo = f.zoneout;
-  l.DENC = c->DMEM.as<float>(); l.ld_denc = D; l.DZ = c->fDZ.as<float>(); l.DHC = c->fDHC.as<float>();
-  l.DCC = c->fDCC.as<float>(); l.DHP = c->fDHP.as<float>();
-  if (fe_enc_fused(c)) {  // d h carried = dZ(t+1)·Wh^T + its direct part, fused with the cell backward
-    const long Bp = (B + 31) & ~31L;
-    for (int d = 0; d < 2; ++d)
-      hipLaunchKernelGGL(k_tr_tf_weights_f32, dim3(1024), dim3(256), 0, s, pvar(c, fe_lstm_scope(d) + "kernel") + (long)C * 4 * U,
-                         (long)4 * U, 0, U, 4 * U, U / 32, (int)TF_PLAIN, U, c->fTWb.as<__bf16>() + (long)d * 4 * U * U);
-    TT2_HIP(hipMemsetAsync(c->fDZh.p, 0, c->fDZh.bytes, s));  // dZ(T) = 0
-    TT2_HIP(hipMemsetAsync(c->fDHP.p, 0, c->fDHP.bytes, s));
-    TrFused e{};
-    e.Wt = c->fTWb.as<__bf16>(); e.wdir = (long)4 * U * U; e.K = 4 * U; e.B = B; e.H = U; e.T = T; e.lens = lens;
-    e.zm = enczm; e.zo = f.zoneout; e.GA = c->fGA.as<float>(); e.CN = c->fCN.as<float>(); e.CS = c->fCS.as<float>();
-    e.DENC = c->DMEM.as<float>(); e.ld_denc = D; e.DZ = c->fDZ.as<float>(); e.DCC = c->fDCC.as<float>();
-    e.DHP = c->fDHP.as<float>(); e.DZh = c->fDZh.as<__bf16>(); e.adir = 2 * Bp * 4 * U;
-    for (int t = T - 1; t >= 0; --t) {
-      e.t = t;
-      hipLaunchKernelGGL(k_tr_fused<TF_EBWD>, dim3(2 * 2 * U / 32), dim3(TLG_NT), 0, s, e);
-    }
-  } else {
-    for (int t = T - 1; t >= 0; --t) {
-      l.t = t;
-      fe_lstm_cell_bwd(l, s);
-      for (int d = 0; d < 2; ++d)
-        tr_gemm(B, U, 4 * U, c->fDZ.as<float>() + ((long)d * T + t) * B * 4 * U, 4 * U,
-                c->fLWhT.as<float>() + (long)d * 4 * U * U, U, c->fDHC.as<float>() + (long)d * B * U, U, s, nullptr,
-                c->fDHP.as<float>() + (long)d * B * U, U);
-    }
-  }
-  for (int d = 0; d < 2; ++d) {  // recurrent weights: Σ_t HS(t)ᵀ DZ(t); biases
-    const long R = (long)T * B;
-    tr_transpose(c->fHS.as<float>() + (long)d * (T + 1) * B * U, R, U, U, FB, R, s);
-    tr_gemm(U, 4 * U, (int)R, FB, R, c->fDZ.as<float>() + (long)d * T * B * 4 * U, 4 * U,
-            gvar(c, fe_lstm_scope(d) + "kernel") + (long)C * 4 * U, 4 * U, s);
-    tr_colsum(c, c->fDZ.as<float>() + (long)d * T * B * 4 * U, R, 4 * U, 4 * U, gvar(c, fe_lstm_scope(d) + "bias"), s);
-  }
-  fe_lstm_dxp(c->fDZ.as<float>(), lens, B, T, U, c->fdXP.as<float>(), s);
-  const float* X3 = c->fEY[f.enc_conv_layers].as<float>();
-  tr_transpose(X3, M, C, C, FB, M, s);
-  float* dxn = c->fdA.as<float>();
-  float* dxo = c->fdB.as<float>();
-  for (int d = 0; d < 2; ++d) {
-    tr_gemm(C, 4 * U, (int)M, FB, M, c->fdXP.as<float>() + d * 4 * U, 8 * U, gvar(c, fe_lstm_scope(d) + "kernel"),
-            4 * U, s);
-    tr_gemm((int)M, C, 4 * U, c->fdXP.as<float>() + d * 4 * U, 8 * U, c->fLWxT.as<float>() + (long)d * 4 * U * C, C,
-            dxn, C, s, nullptr, d ? dxn : nullptr, C);
-  }
-  // encoder convolutions backward (dropout -> BN -> ReLU -> conv)
-  for (int i = f.enc_conv_layers - 1; i >= 0; --i) {
-    const std::string sc = fe_conv_scope(i + 1);
-    const float* mean = BN + (long)i * 2 * 512;
-    const float* var = mean + 512;
-    float* dz = c->fDZc.as<float>();
-    const bool bplanes = c->fePl.p && g_tr_prec == 2;
-    __bf16* bpl = reinterpret_cast<__bf16*>(c->fePl.p);
-    fe_bn_bwd(c, dxn, encm ? encm + (long)i * M * C : nullptr, c->fEA[i].as<float>(), M, C, mean, var, sc, 2,
-              c->fDY.as<float>(), dz, s, bplanes ? bpl : nullptr, T);
-    tr_colsum(c, dz, M, C, C, gvar(c, sc + "conv1d/bias"), s);
-    const int cin = i == 0 ? E : C, pad = (K - 1) / 2;
-    const float* xin = i == 0 ? c->fEX.as<float>() : c->fEY[i].as<float>();
-    if (c->blas_on && g_tr_prec == 2 && 2.0 * K * cin * (double)C * M >= kTrBigMinFlops) {
-      KcConvA cv;  // im2colᵀ gathered straight into gemm_bf16_kc's bf16 operand copy
-      cv.x = xin; cv.xs_b = (long)T * cin; cv.xs_t = cin; cv.B = B; cv.T = T; cv.C = cin; cv.kw = K; cv.pad = pad;
-      gemm_bf16_kc(K * cin, C, (int)M, nullptr, 0, dz, C, gvar(c, sc + "conv1d/kernel"), C, c->blasA, c->blasB,
-                   c->blasP, s, false, &cv);
-      ++c->blas_calls;
-    } else {
-      hipLaunchKernelGGL(k_pn_im2col_t, dim3(nblk((long)K * cin * M)), dim3(256), 0, s, xin, (long)T * cin, (long)cin,
-                         B, T, cin, K, pad, FB, M);
-      tr_gemm(K * cin, C, (int)M, FB, M, dz, C, gvar(c, sc + "conv1d/kernel"), C, s);
-    }
-    hipLaunchKernelGGL(k_pn_flip, dim3(nblk((long)K * cin * C)), dim3(256), 0, s, pvar(c, sc + "conv1d/kernel"), K, cin,
-                       C, WT);
-    if (bplanes) {  // input gradient: conv of the dz planes with the flipped kernel
-      __bf16* bwt = reinterpret_cast<__bf16*>(c->feWt.p);
-      kc_transpose_bf16(WT, K * C, cin, cin, bwt, K * C, (cin + 255) / 256 * 256, s);
-      conv_bf16_planes(bpl, C, B, T, K, bwt, (long)K * C, cin, nullptr, ACT_NONE, dxo, cin, s);
-    } else {
-      GemmArgs g;
-      g.a_mode = A_CONV1D; g.M = (int)M; g.N = cin; g.T = T; g.kw = K; g.pad = K - 1 - pad;
-      g.A = dz; g.C = C; g.xs_b = (long)T * C; g.xs_t = C; g.K = K * C;
-      g.Bw = WT; g.ldb = cin; g.Cout = dxo; g.ldc = cin;
-      tr_gemm_run(g, s);
-    }
-    std::swap(dxn, dxo);
-  }
-  fe_embed_bwd(ids, dxn, M, E, f.n_symbols, gvar(c, vn("inputs_embedding")), s, FB,
-               (long)(c->fFBUF.bytes / sizeof(float)));  // FB is free after the conv loop
 }
 
 
@@ -4609,6 +3549,31 @@ static void tr_d2h(tt2_train_ctx* c, void* dst, const void* src, size_t bytes) {
   } else {
     TT2_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   }
+}
+
+// the environment as tt2_train_create finds it (train_ctx.h TrSwitches documents each switch)
+static TrSwitches tr_read_switches() {
+  TrSwitches w;
+  w.blas = env_on("TT2_TRAIN_BLAS", w.blas);
+  w.values16 = env_on("TT2_TR_VALUES16", w.values16);
+  w.fe_direct = env_on("TT2_FE_CONV_DIRECT", w.fe_direct);
+  w.fe_gru_seq = env_on("TT2_FE_GRU_SEQ", w.fe_gru_seq);
+  w.persist = env_on("TT2_TR_PERSIST", w.persist);
+  w.persist_bwd = env_on("TT2_TR_PERSIST_BWD", w.persist_bwd);
+  w.pn_planes = env_on("TT2_PN_PLANES", w.pn_planes);
+  w.fused = env_on("TT2_TR_FUSED", w.fused);
+  w.e2 = env_on("TT2_TR_E2", w.e2);
+  w.attq = env_on("TT2_TR_ATTQ", w.attq);
+  w.dwloc_cum = env_on("TT2_TR_DWLOC_CUM", w.dwloc_cum);
+  w.tb_dgt = env_on("TT2_TB_DGT", w.tb_dgt);
+  w.tp_oc = env_int("TT2_TP_OC", w.tp_oc);
+  w.tp_stamp = env_int("TT2_TP_STAMP", -1);
+  w.tb_stamp = env_int("TT2_TB_STAMP", -1);
+  w.attq_stamp = env_int("TT2_ATTQ_STAMP", -1);
+  w.tp_stamp_file = env_str("TT2_TP_STAMP_FILE", "tp_stamps.bin");
+  w.tb_stamp_file = env_str("TT2_TB_STAMP_FILE", "tb_stamps.bin");
+  w.attq_stamp_file = env_str("TT2_ATTQ_STAMP_FILE", "attq_stamps.bin");
+  return w;
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------
@@ -4762,17 +3727,9 @@ tt2_status tt2_train_create(const tt2_train_config* cfg, int hip_device, tt2_tra
     TT2_CHECK(hip_device >= 0 && hip_device < n, TT2_ERR_HIP, "no such HIP device");
     TT2_HIP(hipSetDevice(hip_device));
     auto* c = new tt2_train_ctx();
-    if (const char* e = std::getenv("TT2_TRAIN_BLAS")) c->blas_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TT2_TR_VALUES16")) c->values16_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TT2_FE_CONV_DIRECT")) c->fe_direct = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TT2_FE_GRU_SEQ")) c->fe_gru_seq = std::atoi(e) != 0;
-    {
-      const char* e = std::getenv("TT2_TR_PERSIST");
-      c->tp_on = !(e && e[0] == '0') && tp_device_ok(hip_device);
-      // TT2_TR_PERSIST_BWD=0 runs the per-step backward launches instead of the persistent backward
-      const char* eb = std::getenv("TT2_TR_PERSIST_BWD");
-      c->tb_on = !(eb && eb[0] == '0') && tb_device_ok(hip_device);
-    }
+    c->sw = tr_read_switches();
+    c->tp_on = c->sw.persist && tp_device_ok(hip_device);
+    c->tb_on = c->sw.persist_bwd && tb_device_ok(hip_device);
     try {
       c->dev = hip_device;
       c->cfg = *cfg;
@@ -4953,22 +3910,13 @@ tt2_status tt2_train_forward_backward_text_dev(tt2_train_ctx* c, const int32_t* 
     c->last_stream = s;
     TT2_HIP(hipEventRecord(c->ev0, s));
     const float* refs[2] = {ref_emt_d, ref_spk_d};
-    g_tr_kpart = &c->kpart;
-    g_tr_prec = c->cfg.precision ? 2 : 0;
-    g_tr_ctx = c;
     tr_front_forward(c, ids_d, lengths_d, refs, T_ref, enc_conv_masks_d, enc_zoneout_masks_d, T_in, s);
     tr_redzones(c, "front forward");
     tr_forward_backward(c, c->fMEM.as<float>(), lengths_d, targets_d, stop_targets_d, prenet_masks_d, zoneout_masks_d,
                         postnet_masks_d, T_in, T_out, s);
     tr_redzones(c, "decoder + postnet");
-    g_tr_kpart = &c->kpart;
-    g_tr_prec = c->cfg.precision ? 2 : 0;
-    g_tr_ctx = c;
     tr_front_backward(c, ids_d, lengths_d, refs, T_ref, enc_conv_masks_d, enc_zoneout_masks_d, T_in, s);
     tr_redzones(c, "front backward");
-    g_tr_kpart = nullptr;
-    g_tr_prec = 0;
-    g_tr_ctx = nullptr;
     tr_regularize(c, s);
     tr_write_status(c, s);
     TT2_HIP(hipEventRecord(c->ev1, s));

@@ -1084,10 +1084,7 @@ static void wn_generate_dev(tt2_wn_ctx* c, const float* cond_in, int B, int T_f,
     w.gran = reinterpret_cast<unsigned long long*>(c->gran.as<char>() + 16);
     w.w1 = c->w1.p ? c->w1.as<f32x4>() : nullptr;
     w.gb1 = c->gb1.p ? c->gb1.as<float>() : nullptr;
-    static const bool fuse0 = [] {
-      const char* e = std::getenv("TT2_WW_L0HEAD");  // 0: layer 0 on its own work-groups (A/B)
-      return !e || std::atoi(e) != 0;
-    }();
+    static const bool fuse0 = env_on("TT2_WW_L0HEAD", true);  // 0: layer 0 on its own work-groups (A/B)
     w.l0 = fuse0 && c->l0.p ? c->l0.as<float>() : nullptr;
     const void* kern = ww_kernel(R, c->C == 2);
     const unsigned shm = (unsigned)ww_lds_bytes(R, c->C);

@@ -759,10 +759,7 @@ size_t ww_ring_floats(int R, int L, int per) {
 }
 
 bool ww_onehop(int R) {
-  static const bool on = [] {
-    const char* e = std::getenv("TT2_WW_ONEHOP");  // 0: the two-hop R = 256 form
-    return !e || std::atoi(e) != 0;
-  }();
+  static const bool on = env_on("TT2_WW_ONEHOP", true);  // 0: the two-hop R = 256 form
   return R == 256 && on;
 }
 

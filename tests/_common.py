@@ -1,4 +1,5 @@
 """Shared test helpers: configs, seeded synthetic inputs, oracle hparams."""
+import contextlib
 import os
 import shutil
 
@@ -7,6 +8,23 @@ import numpy as np  # noqa: F401
 from oracle.hp import oracle_hp, wavenet_oracle_hp  # noqa: F401
 from tt2.hparams import bench_wavenet_hparams, hparams
 from tt2.synthetic import mol_uniforms, prenet_masks, tacotron_inputs  # noqa: F401
+
+
+@contextlib.contextmanager
+def env(**kv):
+    """Set environment variables (values as strings) for the block; on exit each one gets its
+    earlier value back, or is removed when it was unset.  The libraries read their switches when a
+    context is created (DESIGN.md "Environment switches"), so create the engine / trainer inside."""
+    old = {k: os.environ.get(k) for k in kv}
+    os.environ.update(kv)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def small_hparams():

@@ -11,7 +11,7 @@ ships no checkpoint or fixture of this model (oracle/__init__.py).
 import numpy as np
 import pytest
 
-from _common import full_hparams, oracle_hp, prenet_masks, small_hparams, tacotron_inputs
+from _common import env, full_hparams, oracle_hp, prenet_masks, small_hparams, tacotron_inputs
 from oracle import tacotron_emt_ref as ER
 
 pytestmark = pytest.mark.gpu
@@ -155,7 +155,6 @@ def test_multihead_persistent_matches_launch_path_b32():
     """configs[1]-shaped batch (B = 32, T_ref 400): persistent decoder against the launch path over
     80 free-running steps, same weights, inputs and prenet masks (split fp16x3 vs fp32 MFMA products:
     the two paths agree to float rounding, compared at 1e-3)."""
-    import os
     from tt2.engine import TacotronEngine
     from tt2.weights import init_tacotron_emt_weights
     hp = full_hparams()
@@ -165,15 +164,8 @@ def test_multihead_persistent_matches_launch_path_b32():
     masks = prenet_masks(n, B, hp.prenet_layers[0], seed=7)
     outs = []
     for mode in ("persistent", "launch"):
-        old = os.environ.get("TT2_DECODER")
-        os.environ["TT2_DECODER"] = mode
-        try:
+        with env(TT2_DECODER=mode):
             eng = TacotronEngine(hp, W, B, T, TR, n, 0, False, False, "multihead", "gru", 4)
-        finally:
-            if old is None:
-                del os.environ["TT2_DECODER"]
-            else:
-                os.environ["TT2_DECODER"] = old
         out = eng.synthesize(ids, lens, re, rs, n, masks)
         persistent, _ = eng.decoder_path()
         outs.append((out, eng.emt_alignments(), persistent))
@@ -213,13 +205,9 @@ def test_simple_full_width_persistent_emt_only_and_launch_path():
     32-unit partials summed into one softmax per row over the 8 'gru_multi' heads, the 128-wide context
     as the block's first half, refnet_spk's half folded into a per-row LSTM-1 bias; emt_only (no
     speaker half) too, and the launch path (TT2_DECODER=launch) on the same case."""
-    import os
     _case(full_hparams(), "simple", "gru_multi", emt_only=True, B=3, T=9, T_ref=80, n=12, persistent_expected=1)
-    os.environ["TT2_DECODER"] = "launch"
-    try:
+    with env(TT2_DECODER="launch"):
         _case(full_hparams(), "simple", "gru_multi", B=3, T=9, T_ref=80, n=12, persistent_expected=0)
-    finally:
-        del os.environ["TT2_DECODER"]
 
 
 def test_simple_persistent_configs1_gta_vs_oracle():

@@ -6,7 +6,7 @@ injected uniforms.  Intermediate tensors use the same 1e-4 absolute bound unless
 import numpy as np
 import pytest
 
-from _common import (full_hparams, mol_uniforms, oracle_hp, prenet_masks, small_hparams,
+from _common import (env, full_hparams, mol_uniforms, oracle_hp, prenet_masks, small_hparams,
                      small_wavenet_hparams, tacotron_inputs, wavenet_oracle_hp)
 from oracle import tacotron_ref as TR
 from oracle import wavenet_ref as WR
@@ -322,7 +322,6 @@ def test_persistent_long_inputs_match_oracle(full_setup, B, T, n, constraint):
 def test_persistent_long_inputs_match_launch_path(full_setup):
     """T_in = 300 over 400 steps: the long-input persistent decoder against the per-step launch
     path (the attention walks past position 256 within the horizon)."""
-    import os
     hp, W = full_setup
     B, T, n = 32, 300, 400
     ids, lens, re, rs = tacotron_inputs(B, T, 64, seed=77)
@@ -333,11 +332,8 @@ def test_persistent_long_inputs_match_launch_path(full_setup):
     a = eng.synthesize(ids, lens, re, rs, n, masks)  # timed second launch
     print("T_in=%d persistent decoder: %.2f us/step" % (T, 1e3 * eng.decoder_path()[1] / a["frames"].shape[1]))
     eng.close()
-    os.environ["TT2_DECODER"] = "launch"
-    try:
+    with env(TT2_DECODER="launch"):
         eng2 = _engine(hp, W, B, T, 64, n)
-    finally:
-        del os.environ["TT2_DECODER"]
     b = eng2.synthesize(ids, lens, re, rs, n, masks)
     assert not _persistent(eng2)
     eng2.close()
@@ -350,7 +346,6 @@ def test_persistent_long_inputs_match_launch_path(full_setup):
 def test_persistent_matches_launch_path_long(full_setup):
     """1000-step horizon at configs[1] shapes: persistent decoder vs the per-step launch path
     (both HIP; the oracle is too slow for 1000 steps x 32 rows in a unit test)."""
-    import os
     hp, W = full_setup
     B, T, n = 32, 201, 1000
     ids, lens, re, rs = tacotron_inputs(B, T, 64, seed=31)
@@ -359,11 +354,8 @@ def test_persistent_matches_launch_path_long(full_setup):
     a = eng.synthesize(ids, lens, re, rs, n, masks)
     assert _persistent(eng)
     eng.close()
-    os.environ["TT2_DECODER"] = "launch"
-    try:
+    with env(TT2_DECODER="launch"):
         eng2 = _engine(hp, W, B, T, 64, n)
-    finally:
-        del os.environ["TT2_DECODER"]
     b = eng2.synthesize(ids, lens, re, rs, n, masks)
     assert not _persistent(eng2)
     eng2.close()

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _common import small_hparams
+from _common import env, small_hparams
 from oracle import tacotron_ref as TR
 from oracle import train_ref as TRN
 from oracle.hp import oracle_hp
@@ -592,7 +592,6 @@ def test_gpu_train_bf16_library_gemms_match_kernels():
     multiple of the 64-deep step, M not of the 256-row tile): the forward, the losses and d memory
     are identical (those products only produce terminal weight gradients), every gradient agrees
     to fp32 accumulation-order level, and the context counts the large-product calls."""
-    import os
     from tt2.train import TacotronTrainer
     hp = small_hparams()
     hp.override_from_dict(dict(attention_dim=128, attention_filters=32, prenet_layers=[256, 256],
@@ -601,10 +600,8 @@ def test_gpu_train_bf16_library_gemms_match_kernels():
     W, mem, lens, tg, st, pm, zm = _case(hp, B, T_in, T_out)
     names = TRN.train_var_names()
     res = {}
-    old = os.environ.get("TT2_TRAIN_BLAS")
-    try:
-        for flag in ("1", "0"):
-            os.environ["TT2_TRAIN_BLAS"] = flag
+    for flag in ("1", "0"):
+        with env(TT2_TRAIN_BLAS=flag):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", postnet=False)
             try:
                 tr.forward_backward(mem, lens, tg, st, pm, zm)
@@ -617,11 +614,6 @@ def test_gpu_train_bf16_library_gemms_match_kernels():
             res[flag] = (L, grads, gmem)
             # on: the two LSTM kernel gradients (2e10+ flops each at T·B = 2000); off: none
             assert nblas == (2 if flag == "1" else 0), (flag, nblas)
-    finally:
-        if old is None:
-            os.environ.pop("TT2_TRAIN_BLAS", None)
-        else:
-            os.environ["TT2_TRAIN_BLAS"] = old
     (La, ga, ma), (Lb, gb, mb) = res["1"], res["0"]
     assert La["before"] == Lb["before"] and La["stop_token"] == Lb["stop_token"]
     np.testing.assert_array_equal(ma, mb)
@@ -639,7 +631,6 @@ def test_gpu_train_fused_lstm_matches_split_k_path():
     operand (2^-8 relative), so the gradients agree to bf16-rounding level, not bit for bit: losses
     within 1e-5 relative, every gradient within 1e-2 (Frobenius, relative; measured <= 3e-3 for the
     prenet kernels, the most sensitive; a wrong column or row would be O(1))."""
-    import os
     from tt2.hparams import hparams
     from tt2.train import TacotronTrainer
     hp = hparams.copy()
@@ -651,9 +642,7 @@ def test_gpu_train_fused_lstm_matches_split_k_path():
     zm = zoneout_masks(T_out, B, hp.decoder_lstm_units, seed=3)
     res = {}
     for mode in ("1", "0"):
-        old = os.environ.get("TT2_TR_FUSED")
-        os.environ["TT2_TR_FUSED"] = mode
-        try:
+        with env(TT2_TR_FUSED=mode):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", postnet=False)
             try:
                 tr.forward_backward(mem, lens, tg, st, pm, zm)
@@ -661,11 +650,6 @@ def test_gpu_train_fused_lstm_matches_split_k_path():
                 g = {n: tr.get(n, 1, np.asarray(W[n]).shape) for n in TRN.train_var_names()}
             finally:
                 tr.close()
-        finally:
-            if old is None:
-                del os.environ["TT2_TR_FUSED"]
-            else:
-                os.environ["TT2_TR_FUSED"] = old
         res[mode] = (L, g)
     (La, ga), (Lb, gb) = res["1"], res["0"]
     for k in ("before", "stop_token"):
@@ -836,7 +820,6 @@ def test_gpu_train_fused_encoder_lstm_matches_split_k_path():
     the cell in one launch per step, and dZ·W_h^T + the cell backward) against the split products
     + cell launches (TT2_TR_FUSED=0), like the decoder comparison: losses within 1e-5 relative, every
     gradient within 1e-2 (bf16 operand rounding level)."""
-    import os
     from tt2.train import TacotronTrainer
     hp = small_hparams()
     hp.override_from_dict(dict(encoder_lstm_units=256, enc_conv_channels=128, embedding_dim=128))
@@ -844,9 +827,7 @@ def test_gpu_train_fused_encoder_lstm_matches_split_k_path():
     B, T_in, T_out = ids.shape[0], ids.shape[1], tg.shape[1]
     res = {}
     for mode in ("1", "0"):
-        old = os.environ.get("TT2_TR_FUSED")
-        os.environ["TT2_TR_FUSED"] = mode
-        try:
+        with env(TT2_TR_FUSED=mode):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", frontend=True, max_T_ref=re.shape[1])
             try:
                 tr.forward_backward_text(ids, lens, re, rs, tg, st, pm, zm, pnm, em, ezm)
@@ -854,11 +835,6 @@ def test_gpu_train_fused_encoder_lstm_matches_split_k_path():
                 g = {n: tr.get(n, 1, np.asarray(W[n]).shape) for n in TRN.frontend_var_names()}
             finally:
                 tr.close()
-        finally:
-            if old is None:
-                del os.environ["TT2_TR_FUSED"]
-            else:
-                os.environ["TT2_TR_FUSED"] = old
         res[mode] = (L, g)
     (La, ga), (Lb, gb) = res["1"], res["0"]
     for k in ("before", "after"):
@@ -877,7 +853,6 @@ def test_gpu_train_im2col_gathered_large_products_match_kernels():
     TT2_TRAIN_BLAS=0 (fp32 transposes / im2colᵀ + gemm_x3_kernel).  The 512-channel Postnet convs
     are 2·5·512·512·(8·960) >= 2e10 flops, so the gathered form runs.  Losses within 1e-5 relative,
     every gradient within 2e-2 (bf16 operand rounding, K split / accumulation order)."""
-    import os
     from tt2.train import TacotronTrainer
     hp = small_hparams()
     hp.override_from_dict(dict(reference_filters=[32, 32, 64, 64, 128, 128], postnet_channels=512))
@@ -885,10 +860,8 @@ def test_gpu_train_im2col_gathered_large_products_match_kernels():
     B, T_in, T_out = ids.shape[0], ids.shape[1], tg.shape[1]
     names = TRN.frontend_var_names() + TRN.postnet_var_names()
     res = {}
-    old = os.environ.get("TT2_TRAIN_BLAS")
-    try:
-        for flag in ("1", "0"):
-            os.environ["TT2_TRAIN_BLAS"] = flag
+    for flag in ("1", "0"):
+        with env(TT2_TRAIN_BLAS=flag):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", frontend=True, max_T_ref=re.shape[1])
             try:
                 tr.forward_backward_text(ids, lens, re, rs, tg, st, pm, zm, pnm, em, ezm)
@@ -897,11 +870,6 @@ def test_gpu_train_im2col_gathered_large_products_match_kernels():
             finally:
                 tr.close()
             res[flag] = (L, g)
-    finally:
-        if old is None:
-            os.environ.pop("TT2_TRAIN_BLAS", None)
-        else:
-            os.environ["TT2_TRAIN_BLAS"] = old
     (La, ga), (Lb, gb) = res["1"], res["0"]
     for k in ("before", "after"):
         assert abs(La[k] - Lb[k]) < 1e-5 * abs(Lb[k]), (k, La[k], Lb[k])
@@ -919,7 +887,6 @@ def test_gpu_train_postnet_planes_match_im2col(T_out):
     1e-4 relative (measured 1.7e-5: a 3e-7 tanh difference flips the bf16 rounding of some next-layer
     inputs), every decoder and Postnet gradient within 2e-2 (bf16 operand rounding, tanh on
     v_exp/v_rcp against libm, accumulation order)."""
-    import os
     from tt2.train import TacotronTrainer
     hp = small_hparams()
     hp.override_from_dict(dict(postnet_channels=512))
@@ -928,10 +895,8 @@ def test_gpu_train_postnet_planes_match_im2col(T_out):
     pnm = postnet_masks(hp.postnet_num_layers, B, T_out, hp.postnet_channels, seed=3)
     names = TRN.train_var_names() + TRN.postnet_var_names()
     res = {}
-    old = os.environ.get("TT2_PN_PLANES")
-    try:
-        for flag in ("1", "0"):
-            os.environ["TT2_PN_PLANES"] = flag
+    for flag in ("1", "0"):
+        with env(TT2_PN_PLANES=flag):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", postnet=True)
             try:
                 tr.forward_backward(mem, lens, tg, st, pm, zm, pnm)
@@ -940,11 +905,6 @@ def test_gpu_train_postnet_planes_match_im2col(T_out):
             finally:
                 tr.close()
             res[flag] = (L, g)
-    finally:
-        if old is None:
-            os.environ.pop("TT2_PN_PLANES", None)
-        else:
-            os.environ["TT2_PN_PLANES"] = old
     (La, ga), (Lb, gb) = res["1"], res["0"]
     assert abs(La["after"] - Lb["after"]) < 1e-4 * abs(Lb["after"]), (La["after"], Lb["after"])
     for n in ga:
@@ -966,7 +926,6 @@ def test_gpu_train_encoder_planes_match_im2col():
     1e-4 relative, gradients within 5e-2 (measured up to 2.2e-2: the same bf16 operands summed in
     another order move the ReLU / BN-sensitive front-end gradients, e.g. the GST weight norm g, by
     about that much)."""
-    import os
     from tt2.train import TacotronTrainer
     hp = small_hparams()
     hp.override_from_dict(dict(enc_conv_channels=128, embedding_dim=128, encoder_lstm_units=64))
@@ -974,10 +933,8 @@ def test_gpu_train_encoder_planes_match_im2col():
     B, T_in, T_out = ids.shape[0], ids.shape[1], tg.shape[1]
     names = TRN.frontend_var_names() + TRN.postnet_var_names()
     res = {}
-    old = os.environ.get("TT2_PN_PLANES")
-    try:
-        for flag in ("1", "0"):
-            os.environ["TT2_PN_PLANES"] = flag
+    for flag in ("1", "0"):
+        with env(TT2_PN_PLANES=flag):
             tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", frontend=True, max_T_ref=re.shape[1])
             try:
                 tr.forward_backward_text(ids, lens, re, rs, tg, st, pm, zm, pnm, em, ezm)
@@ -986,11 +943,6 @@ def test_gpu_train_encoder_planes_match_im2col():
             finally:
                 tr.close()
             res[flag] = (L, g)
-    finally:
-        if old is None:
-            os.environ.pop("TT2_PN_PLANES", None)
-        else:
-            os.environ["TT2_PN_PLANES"] = old
     (La, ga), (Lb, gb) = res["1"], res["0"]
     for k in ("before", "after"):
         assert abs(La[k] - Lb[k]) < 1e-4 * abs(Lb[k]), (k, La[k], Lb[k])
@@ -1004,15 +956,12 @@ def test_gpu_train_encoder_planes_match_im2col():
         assert rel < 5e-2, (n, rel)
 
 
-def _trainer_run(hp, W, case, env, postnet=False):
+def _trainer_run(hp, W, case, switches, postnet=False):
     """One bf16 forward/backward under the given TT2_* environment (read at context creation)."""
-    import os
     from tt2.train import TacotronTrainer
     mem, lens, tg, st, pm, zm = case
     B, T_in, T_out = tg.shape[0], mem.shape[1], tg.shape[1]
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with env(**switches):
         tr = TacotronTrainer(hp, W, B, T_in, T_out, 0, precision="bf16", postnet=postnet)
         try:
             tr.forward_backward(mem, lens, tg, st, pm, zm)
@@ -1024,12 +973,6 @@ def _trainer_run(hp, W, case, env, postnet=False):
             persist_bwd = float(tr.get("diag:persist_bwd", 0, (1,))[0])
         finally:
             tr.close()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     return dict(L=L, fr=fr, sl=sl, al=al, g=g, gmem=gmem, persist=persist, persist_bwd=persist_bwd)
 
 
@@ -1303,7 +1246,6 @@ def test_gpu_refnet_conv_backward_direct_matches_im2col(precision, tol):
     forward's fp32 FMA against split fp16x3 moves every later gradient by ~2e-5): every gradient
     within 1e-4 of its max; bf16: the moved forward re-rounds the whole bf16 step, so losses within
     1e-5 and the global gradient norm within 2 % (the criteria of the configs[4] fp32-vs-bf16 test)."""
-    import os
     from tt2.hparams import hparams
     from tt2.train import TacotronTrainer
     hp = hparams.copy()
@@ -1312,15 +1254,8 @@ def test_gpu_refnet_conv_backward_direct_matches_im2col(precision, tol):
     names = TRN.frontend_var_names() + TRN.train_var_names() + TRN.postnet_var_names()
     out = []
     for direct in ("1", "0"):
-        old = os.environ.get("TT2_FE_CONV_DIRECT")
-        os.environ["TT2_FE_CONV_DIRECT"] = direct
-        try:
+        with env(TT2_FE_CONV_DIRECT=direct):
             tr = TacotronTrainer(hp, W, 4, 12, 6, 0, frontend=True, max_T_ref=96, precision=precision)
-        finally:
-            if old is None:
-                os.environ.pop("TT2_FE_CONV_DIRECT", None)
-            else:
-                os.environ["TT2_FE_CONV_DIRECT"] = old
         try:
             tr.forward_backward_text(ids, lens, re, rs, tg, st, pm, zm, pnm, em, ezm)
             L = tr.losses()
@@ -1357,7 +1292,6 @@ def test_gpu_refnet_gru_sequence_kernels_match_per_step(precision, tol, ltol):
     recurrence; losses 1e-5); bf16: the per-step products round to bf16, the sequence kernels stay
     fp32, and the moved style embedding re-rounds the whole bf16 step (losses 1e-3, global gradient
     norm 2 %, the criteria of the configs[4] fp32-vs-bf16 test)."""
-    import os
     from tt2.hparams import hparams
     from tt2.train import TacotronTrainer
     hp = hparams.copy()
@@ -1366,15 +1300,8 @@ def test_gpu_refnet_gru_sequence_kernels_match_per_step(precision, tol, ltol):
     names = TRN.frontend_var_names() + TRN.train_var_names() + TRN.postnet_var_names()
     out = []
     for seq in ("1", "0"):
-        old = os.environ.get("TT2_FE_GRU_SEQ")
-        os.environ["TT2_FE_GRU_SEQ"] = seq
-        try:
+        with env(TT2_FE_GRU_SEQ=seq):
             tr = TacotronTrainer(hp, W, 4, 12, 6, 0, frontend=True, max_T_ref=400, precision=precision)
-        finally:
-            if old is None:
-                os.environ.pop("TT2_FE_GRU_SEQ", None)
-            else:
-                os.environ["TT2_FE_GRU_SEQ"] = old
         try:
             tr.forward_backward_text(ids, lens, re, rs, tg, st, pm, zm, pnm, em, ezm)
             L = tr.losses()
@@ -1397,3 +1324,57 @@ def test_gpu_refnet_gru_sequence_kernels_match_per_step(precision, tol, ltol):
             assert _rel(ga[n], gb[n]) < tol, (n, _rel(ga[n], gb[n]), worst)
         else:
             assert np.abs(ga[n]).max() < 1e-6, n
+
+
+@pytest.mark.gpu
+def test_gpu_train_two_live_contexts_do_not_share_state():
+    """Two trainers alive at once on one thread, A bf16 (the persistent forward and backward at the
+    fork widths) and B fp32, stepped in the order A, B, A on the same inputs: A's second result and
+    B's equal what a fresh trainer of the same precision produces alone.  Every product reads its
+    precision, split-K scratch and bf16 operand copies from the context it is handed, so nothing of
+    B's call may reach A's.  Two solo runs at this shape are bit-identical (measured: spread 0 for
+    the losses and all 19 gradients, both precisions, before and after this refactor; there are no
+    atomics in the step), so the comparison is array_equal."""
+    from tt2.hparams import hparams
+    from tt2.train import TacotronTrainer
+    hp = hparams.copy()
+    hp.override_from_dict(dict(tacotron_num_gpus=1))
+    B, T_in, T_out = 5, 7, 3
+    W = init_tacotron_weights(hp, seed=5339)
+    mem, lens, tg, st = train_batch(B, T_in, T_out, memory_width(hp), seed=7)
+    pm = prenet_masks(T_out, B, hp.prenet_layers[0], seed=7)
+    zm = zoneout_masks(T_out, B, hp.decoder_lstm_units, seed=7)
+    names = TRN.train_var_names()
+
+    def make(precision):
+        return TacotronTrainer(hp, W, B, T_in, T_out, 0, precision=precision, postnet=False)
+
+    def step(tr):
+        tr.forward_backward(mem, lens, tg, st, pm, zm)
+        return tr.losses(), {n: tr.get(n, 1, np.asarray(W[n]).shape) for n in names}
+
+    solo = {}
+    for precision in ("bf16", "fp32"):
+        tr = make(precision)
+        try:
+            solo[precision] = step(tr)
+        finally:
+            tr.close()
+    a, b = make("bf16"), make("fp32")
+    try:
+        step(a)
+        got_b = step(b)
+        got_a = step(a)
+        assert a.get("diag:persist", 0, (1,))[0] == 1.0 and a.get("diag:persist_bwd", 0, (1,))[0] == 1.0
+        assert b.get("diag:persist", 0, (1,))[0] == 0.0
+    finally:
+        a.close()
+        b.close()
+    for precision, (L, g) in (("bf16", got_a), ("fp32", got_b)):
+        Ls, gs = solo[precision]
+        worst = max(float(np.abs(g[n] - gs[n]).max()) for n in names)
+        print("{}: interleaved against solo, max |d grad| {:.3e}, losses {} {}".format(precision, worst, L, Ls))
+        for k in ("before", "stop_token", "regularization", "loss"):
+            assert L[k] == Ls[k], (precision, k, L[k], Ls[k])
+        for n in names:
+            np.testing.assert_array_equal(g[n], gs[n], err_msg="{} {}".format(precision, n))
