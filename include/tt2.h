@@ -260,6 +260,12 @@ tt2_status tt2_decoder_path(tt2_ctx* ctx, int* persistent, float* kernel_ms);
 /* Persistent decode run with env TT2_STAMP_STEP=k: s_memrealtime (100 MHz) stamps [256 work-groups]
  * [32 stage points] of step k (k_decode_persist PD_STAMP sites).  Diagnostic only. */
 tt2_status tt2_debug_pd_stamps(tt2_ctx* ctx, long long* out8192);
+/* Host-side split of fp32 values into the pre-split fp16 operands the persistent decoder multiplies
+ * (csrc/common.h kg_pack; no device needed): for every 4 floats x[4i .. 4i+3] (n % 4 == 0) writes
+ * 8 fp16 bit patterns out[8i .. 8i+7] = {hi0..hi3, lo0..lo3}, hi = fp16(x), lo = fp16(x - hi).
+ * The same arithmetic splits the resident weights at finalize and the exchanged activations in the
+ * kernel.  Diagnostic only. */
+tt2_status tt2_debug_kg_pack(const float* x, long long n, uint16_t* out);
 /* Measured HBM bandwidth of this device (the spec peak confirmed on the box): a
  * STREAM-like copy between two `bytes`-sized device buffers (choose >> the 256 MB MALL), 16-byte
  * loads/stores; *gbps = (read + write bytes) / the best of `iters` timed copies, in GB/s.  No

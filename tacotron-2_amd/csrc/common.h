@@ -189,13 +189,49 @@ __host__ __device__ inline int wf_idx(int k, int j) {  // within one 16-column t
 // +1.1 us per decoder step (A/B, round 2) for no parity gain.
 constexpr float KG_SB = 1024.f, KG_UNSCALE = 1.f / 1024.f, KG_BMAX = 63.9f;
 typedef _Float16 kg_f16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void kg_split(const f32x4& v, kg_f16x4& h, kg_f16x4& l) {
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// v = hi + lo (+ <= 2^-22 relative): hi = fp16(v), lo = fp16(v - hi), both round-to-nearest-even.
+// Host and device give the same bits (tt2_debug_kg_pack, tests/test_split_pack.py).
+__host__ __device__ inline void kg_split1(float v, _Float16& h, _Float16& l) {
+  h = (_Float16)v;
+  l = (_Float16)(v - (float)h);
+}
+__host__ __device__ inline void kg_split(const f32x4& v, kg_f16x4& h, kg_f16x4& l) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const _Float16 x = (_Float16)v[e];
+    _Float16 x, y;
+    kg_split1(v[e], x, y);
     h[e] = x;
-    l[e] = (_Float16)(v[e] - (float)x);
+    l[e] = y;
   }
+}
+// Pre-split operand: the four hi and the four lo halves of one AF/WF float4 -- the 16 bytes of the
+// float4 itself, ready as the two operand pairs of kg_mfma_x3_pre.  A value that stays the same from
+// step to step (a resident weight), or that one thread produces and many consume (an exchanged
+// activation), is split once where it is made instead of by every product that reads it.
+struct alignas(16) kg_pk {
+  kg_f16x4 h, l;
+};
+__host__ __device__ inline kg_pk kg_pack(const f32x4& v) {
+  kg_pk p;
+  kg_split(v, p.h, p.l);
+  return p;
+}
+__host__ __device__ inline kg_pk kg_pk_bits(const u32x4& w) { return __builtin_bit_cast(kg_pk, w); }
+__host__ __device__ inline u32x4 kg_bits(const kg_pk& p) { return __builtin_bit_cast(u32x4, p); }
+// one 16-byte load of a stored operand
+__device__ __forceinline__ kg_pk kg_ld(const float* base, int i4) {
+  return kg_pk_bits(reinterpret_cast<const u32x4*>(base)[i4]);
+}
+// kg_mfma_x3 from pre-split operands: the same six MFMAs in the same order
+__device__ __forceinline__ void kg_mfma_x3_pre(const kg_pk& a0, const kg_pk& a1, const kg_pk& bw, f32x4& c0,
+                                               f32x4& c1) {
+  c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(a0.l, bw.h, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1.l, bw.h, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(a0.h, bw.l, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1.h, bw.l, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(a0.h, bw.h, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1.h, bw.h, c1, 0, 0, 0);
 }
 // bw is the pre-scaled (x KG_SB) weight fragment; c0/c1 accumulate A·B·2^10.
 __device__ __forceinline__ void kg_mfma_x3(const f32x4& a0, const f32x4& a1, const f32x4& bw, f32x4& c0,

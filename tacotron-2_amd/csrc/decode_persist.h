@@ -42,7 +42,8 @@ struct PdArgs {
   int stop_at_any, mask_encoder, cumulative, constraint, monotonic, win;
   float zo, one_m_zo;
   int poll_sleep;       // s_sleep(1) repetitions between flag polls (env TT2_PD_SLEEP)
-  // weights (tacotron.hip finalize layouts)
+  // weights (tacotron.hip finalize layouts); the WF ones are x KG_SB and pre-split: one kg_pk (common.h)
+  // in place of every float4
   const float* l1_w;    // [256 tiles][768 x 16] WF, rows [prenet | context_enc]
   const float* l1_wh;   // [256][1024 x 16] recurrent rows
   const float* l1_b;    // [4096] lstm column order
@@ -65,13 +66,13 @@ struct PdArgs {
   const int* lengths;   // [B]
   const uint8_t* masks; // [max_iters][2][B][256] prenet keep bits
   // exchange buffers, two step parities each
-  float* H1x;   // [2][32 x 1024] AF: h1_new
-  float* H2x;   // [2][32 x 1024] AF: h2_new
+  float* H1x;   // [2][32 x 1024] AF: h1_new, every float4 pre-split (kg_pk: untagged under the flag protocol)
+  float* H2x;   // [2][32 x 1024] AF: h2_new, every float4 in exchange form (decode_persist.hip pd_xchg)
   unsigned long long* Eg;  // [2][32 rows][8 slices][TM t] {tag, partial energy} granules
-  float* CTXx;  // [2][32 x 512] AF: context_enc
+  float* CTXx;  // [2][32 x 512] AF: context_enc, same
   float* SSx;   // [2][32]: Σ_{t<len} alignments (style-context scale)
   unsigned long long* PPg; // [2][8 splits][32 rows][352] {tag, projection partial} granules
-  unsigned long long* PREg;  // [2][32 x 256] AF-ordered {tag = step<<1 | stop bit, prenet output} granules
+  unsigned long long* PREg;  // [2][32 x 256] AF-ordered {tag = step<<1 | stop bit, prenet output split hi | lo << 16} granules
   // outputs
   float* frames;  // [B][max_iters][nm]
   float* stop;    // [B][max_iters]

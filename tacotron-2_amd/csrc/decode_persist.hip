@@ -38,7 +38,7 @@
 
 namespace tt2 {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 typedef __attribute__((address_space(1))) float pd_gf32;
 typedef __attribute__((address_space(1))) unsigned pd_gu32;
@@ -60,9 +60,14 @@ __device__ __forceinline__ float pd_ld(const float* p) {
   return __hip_atomic_load((pd_gf32*)const_cast<float*>(p), PD_RLX);
 }
 __device__ __forceinline__ void pd_st(float* p, float v) { __hip_atomic_store((pd_gf32*)p, v, PD_RLX); }
-__device__ __forceinline__ f32x4 pd_ld4(const float* base, int i4) {
+__device__ __forceinline__ u32x4 pd_ld4(const float* base, int i4) {
   const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, i4 * 16, 0, 16));
+  return __builtin_amdgcn_raw_buffer_load_b128(r, i4 * 16, 0, 16);
+}
+__device__ __forceinline__ f32x4 pd_ld4f(const float* base, int i4) { return __builtin_bit_cast(f32x4, pd_ld4(base, i4)); }
+__device__ __forceinline__ u32x2 pd_ld2(const float* base, int i2) {
+  const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
+  return __builtin_amdgcn_raw_buffer_load_b64(r, i2 * 8, 0, 16);
 }
 
 // Wave-uniform bounded spin: poll until cond() holds on every lane.  false on timeout (2 s) or
@@ -147,8 +152,15 @@ __device__ __forceinline__ bool pd_block_wait(int* slot, F poll) {
 
 // Data-tagged 8-byte granule {tag, fp32 bits}: the data is the flag (Guideline 16 R2) -- no drain,
 // no separate flag round trip.  For the small intra-row exchanges (energies, projection partials).
-__device__ __forceinline__ void pd_put(unsigned long long* g, unsigned tag, float v) {
-  __hip_atomic_store((pd_gu64*)g, ((unsigned long long)tag << 32) | __float_as_uint(v), PD_RLX);
+__device__ __forceinline__ void pd_putw(unsigned long long* g, unsigned tag, unsigned w) {
+  __hip_atomic_store((pd_gu64*)g, ((unsigned long long)tag << 32) | w, PD_RLX);
+}
+__device__ __forceinline__ void pd_put(unsigned long long* g, unsigned tag, float v) { pd_putw(g, tag, __float_as_uint(v)); }
+// One value pre-split for the consumers' MFMAs (the prenet granules): hi | lo << 16.
+__device__ __forceinline__ unsigned pd_split1(float v) {
+  _Float16 h, l;
+  kg_split1(v, h, l);
+  return (unsigned)__builtin_bit_cast(unsigned short, h) | ((unsigned)__builtin_bit_cast(unsigned short, l) << 16);
 }
 // Each active lane fetches N granules base[off + i*stride] (base wave-uniform) until every tag ==
 // tag (wave-uniform bounded spin).  false: timeout or a peer failed.
@@ -187,28 +199,55 @@ __device__ __forceinline__ bool pd_take(const PdArgs& a, int ph, const unsigned 
   }
 }
 
-// Self-tagged exchange values (h1, h2, context slices, Σ align): bit 0 of every fp32 value written at
-// step t carries tb(t) = ((t >> 1) & 1) ^ 1.  A buffer of parity t & 1 otherwise holds step t-2's
-// values (the other tag bit) or the per-launch zeros (bit 0 = 0 never matches steps 0, 1), so a
-// consumer can check every value it loaded: the producer needs no drain before its flag, and the
-// consumer no flag round trip before its data load when the data has landed.  The flag stays as a
-// hint polled only after an optimistic load missed.  Cost: one ulp (2^-23 relative) on exchanged
-// values, below the split fp16x3 products' own 2^-22.
+// Self-tagged exchange values (h2, context slices, Σ align; h1 under PD_TAG_H1): every 8-byte granule
+// written at step t carries tb(t) = ((t >> 1) & 1) ^ 1 -- in bit 0 of the fp32 value (Σ align), or, for
+// the pre-split float4s below, in bit 0 of the granule's lo word.  A buffer of parity t & 1 otherwise
+// holds step t-2's values (the other tag bit) or the per-launch zeros (bit 0 = 0 never matches steps
+// 0, 1), so a consumer can check every granule it loaded: the producer needs no drain before its flag,
+// and the consumer no flag round trip before its data load when the data has landed.  The flag stays
+// as a hint polled only after an optimistic load missed.  Cost: one ulp of an fp32 value (2^-23
+// relative) or of a lo half (<= 2^-22 relative to the value, 2^-24 absolute where lo = 0): the class
+// of the split fp16x3 products' own 2^-22.
+//
+// Exchange form of an AF float4 v (h2, context; h1 under PD_TAG_H1): {H01, L01, H23, L23}, Hij / Lij =
+// the hi / lo fp16 halves (kg_split) of v[i] | v[j] << 16.  Each 8-byte half -- the granule the memory system was
+// observed to keep untorn (MI355X_MICROARCH.md § visibility) -- holds its own tag bit, in a lo half
+// and never a hi half.  The producer splits once; each of the 256 consumers forms the MFMA operand
+// pairs with pd_unx (register moves) instead of re-splitting the fp32 values.
+// Untagged data (tb > 1: h1 under the flag protocol) needs no tag bit per granule and is stored as the
+// operand itself, {H01, H23, L01, L23}: its consumers use the loaded registers as they are.
+__device__ __forceinline__ u32x4 pd_xchg(const f32x4& v, unsigned tb) {
+  const u32x4 w = kg_bits(kg_pack(v));  // {H01, H23, L01, L23}
+  if (tb > 1u) return w;
+  return u32x4{w[0], (w[2] & ~1u) | tb, w[1], (w[3] & ~1u) | tb};
+}
+__device__ __forceinline__ kg_pk pd_unx(const u32x4& x) { return kg_pk_bits(u32x4{x[0], x[2], x[1], x[3]}); }
+// The prenet granules' payloads {h | l << 16} of the 4 values of a float4 -> operand pairs (byte permutes).
+__device__ __forceinline__ kg_pk pd_ung(const u32x4& g) {
+  return kg_pk_bits(u32x4{__builtin_amdgcn_perm(g[1], g[0], 0x05040100u), __builtin_amdgcn_perm(g[3], g[2], 0x05040100u),
+                          __builtin_amdgcn_perm(g[1], g[0], 0x07060302u), __builtin_amdgcn_perm(g[3], g[2], 0x07060302u)});
+}
+// fp32 value of half e (0, 1) of one exchange granule {Hij, Lij}: hi + lo
+__device__ __forceinline__ float pd_val(const u32x2& g, int e) {
+  const unsigned sh = 16u * e;
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)(g[0] >> sh)) +
+         (float)__builtin_bit_cast(_Float16, (unsigned short)(g[1] >> sh));
+}
 __device__ __forceinline__ unsigned pd_tb(int t) { return ((unsigned)(t >> 1) & 1u) ^ 1u; }
 __device__ __forceinline__ float pd_tag(float v, unsigned tb) { return __uint_as_float((__float_as_uint(v) & ~1u) | tb); }
 __device__ __forceinline__ bool pd_ok1(float v, unsigned tb) { return ((__float_as_uint(v) ^ tb) & 1u) == 0u; }
-__device__ __forceinline__ bool pd_ok4(const f32x4& v, unsigned tb) {
-  return (((__float_as_uint(v[0]) ^ tb) | (__float_as_uint(v[1]) ^ tb) | (__float_as_uint(v[2]) ^ tb) |
-           (__float_as_uint(v[3]) ^ tb)) & 1u) == 0u;
-}
+__device__ __forceinline__ bool pd_ok4(const u32x4& v, unsigned tb) { return (((v[1] ^ tb) | (v[3] ^ tb)) & 1u) == 0u; }
+__device__ __forceinline__ bool pd_ok2(const u32x2& v, unsigned tb) { return ((v[1] ^ tb) & 1u) == 0u; }
 
-// Wave-level take of N self-tagged values X[idx(i)] (sc1 loads; V = f32x4 or float).  The first pass
-// is optimistic; after a miss hint() runs once (a flag poll: the producers have at least issued
+// Wave-level take of N self-tagged values X[idx(i)] (sc1 loads; V = u32x4: a float4 in exchange form,
+// u32x2: one 8-byte granule of it, or float).  The first pass is optimistic; after a miss hint() runs once (a flag poll: the producers have at least issued
 // their stores) and the loads repeat until every value carries tb (bounded spin; one copy of the
 // loads in the loop keeps the register footprint of the fast path).  false: timeout or a peer failed.
-__device__ __forceinline__ f32x4 pd_ldv(const float* X, int i, f32x4) { return pd_ld4(X, i); }
+__device__ __forceinline__ u32x4 pd_ldv(const float* X, int i, u32x4) { return pd_ld4(X, i); }
+__device__ __forceinline__ u32x2 pd_ldv(const float* X, int i, u32x2) { return pd_ld2(X, i); }
 __device__ __forceinline__ float pd_ldv(const float* X, int i, float) { return pd_ld(X + i); }
-__device__ __forceinline__ bool pd_okv(const f32x4& v, unsigned tb) { return pd_ok4(v, tb); }
+__device__ __forceinline__ bool pd_okv(const u32x4& v, unsigned tb) { return pd_ok4(v, tb); }
+__device__ __forceinline__ bool pd_okv(const u32x2& v, unsigned tb) { return pd_ok2(v, tb); }
 __device__ __forceinline__ bool pd_okv(float v, unsigned tb) { return pd_ok1(v, tb); }
 template <int N, class V, class I, class H>
 __device__ __forceinline__ bool pd_takev(const PdArgs& a, int ph, const float* X, I idx, unsigned tb, V (&v)[N],
@@ -236,7 +275,7 @@ __device__ __forceinline__ bool pd_takev(const PdArgs& a, int ph, const float* X
   }
 }
 template <int N, class I, class H>
-__device__ __forceinline__ bool pd_take4(const PdArgs& a, int ph, const float* X, I idx, unsigned tb, f32x4 (&v)[N],
+__device__ __forceinline__ bool pd_take4(const PdArgs& a, int ph, const float* X, I idx, unsigned tb, u32x4 (&v)[N],
                                          H hint) {
   return pd_takev<N>(a, ph, X, idx, tb, v, hint);
 }
@@ -247,19 +286,17 @@ __device__ __forceinline__ bool pd_take1(const PdArgs& a, int ph, const float* X
 }
 
 // LSTM epilogue store: the 4 hidden units this work-group owns for row em (pd_unit) are one AF
-// float4, held by the 4 consecutive lanes eu = 0..3; lane eu = 0 writes it as ONE 16-byte
-// write-through store (rows 0..15 / 16..31 of a work-group fill 256 contiguous bytes each),
-// every value self-tagged with tb (tb = ~0u: stored as computed, for the flag protocol).
+// float4, held by the 4 consecutive lanes eu = 0..3; lane eu = 0 writes it pre-split (pd_xchg) as ONE
+// 16-byte write-through store (rows 0..15 / 16..31 of a work-group fill 256 contiguous bytes each),
+// both granules self-tagged with tb (tb = ~0u: untagged operand form, for the flag protocol).
+__device__ __forceinline__ void pd_st_x4(float* X, int i4, const f32x4& v, unsigned tb) {
+  const auto r = __builtin_amdgcn_make_buffer_rsrc(X, (short)0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(pd_xchg(v, tb), r, i4 * 16, 0, 16);  // sc1
+}
 __device__ __forceinline__ void pd_st_h4(float* X, int em, int u0, float hn, int lane, unsigned tb) {
   const int src = lane & ~3;
-  const auto tg = [&](float v) { return tb > 1u ? v : pd_tag(v, tb); };
-  const float v0 = tg(__shfl(hn, src)), v1 = tg(__shfl(hn, src + 1));
-  const float v2 = tg(__shfl(hn, src + 2)), v3 = tg(__shfl(hn, src + 3));
-  if ((lane & 3) == 0) {
-    const auto r = __builtin_amdgcn_make_buffer_rsrc(X, (short)0, 0x7fffffff, 0x00020000);
-    const u32x4 d = {__float_as_uint(v0), __float_as_uint(v1), __float_as_uint(v2), __float_as_uint(v3)};
-    __builtin_amdgcn_raw_buffer_store_b128(d, r, af_idx(em, u0) * 4, 0, 16);  // sc1
-  }
+  const f32x4 v = {__shfl(hn, src), __shfl(hn, src + 1), __shfl(hn, src + 2), __shfl(hn, src + 3)};
+  if ((lane & 3) == 0) pd_st_x4(X, af_idx(em, u0) >> 2, v, tb);
 }
 
 // Every storing wave drains its sc1 stores, then one lane raises this work-group's flag.
@@ -285,11 +322,6 @@ __device__ __forceinline__ void pd_publish_rep(const PdArgs& a, int r, unsigned 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid < PD_NREP) __hip_atomic_store((pd_gu32*)(a.rflags + (r * PD_NREP + tid) * PD_NB + blockIdx.x), val, PD_RLX);
-}
-
-// acc(rows 0..15 | 16..31) += A(k-group) · W(k-group, 16 columns), split fp16x3 (common.h)
-__device__ __forceinline__ void kg_mfma(const f32x4& a0, const f32x4& a1, const f32x4& bw, f32x4& c0, f32x4& c1) {
-  kg_mfma_x3(a0, a1, bw, c0, c1);
 }
 
 // Partial tile of wave w -> red[w][32][16] (the MFMA D layout transposed to row-major).
@@ -336,16 +368,29 @@ template <bool EMT, int TM, bool FL>
 __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   static_assert(TM == PD_TMAX || (TM == PD_TMAX_LONG && !EMT), "k_decode_persist geometry");
   static_assert(!FL || (!EMT && TM == PD_TMAX), "floor instance: the Tacotron decoder only");
-  // split fp16x3 product, or (FL) its operands sunk
-  const auto mm = [](const f32x4& a0, const f32x4& a1, const f32x4& bw, f32x4& c0, f32x4& c1) {
-    if constexpr (FL) asm volatile("" ::"v"(a0), "v"(a1), "v"(bw));
-    else kg_mfma(a0, a1, bw, c0, c1);
+  // acc(rows 0..15 | 16..31) += A(k-group) · W(k-group, 16 columns), split fp16x3 from pre-split
+  // operands (common.h), or (FL) the operands sunk as loaded.  mm: activations in exchange form;
+  // mmg: as the payloads of 4 prenet granules; mmf: as fp32 (the EMT-only exchanges).
+  const auto mm = [](const u32x4& x0, const u32x4& x1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
+    if constexpr (FL) asm volatile("" ::"v"(x0), "v"(x1), "v"(kg_bits(bw)));
+    else kg_mfma_x3_pre(pd_unx(x0), pd_unx(x1), bw, c0, c1);
+  };
+  const auto mmo = [](const u32x4& x0, const u32x4& x1, const kg_pk& bw, f32x4& c0, f32x4& c1) {  // untagged h1
+    if constexpr (FL) asm volatile("" ::"v"(x0), "v"(x1), "v"(kg_bits(bw)));
+    else kg_mfma_x3_pre(kg_pk_bits(x0), kg_pk_bits(x1), bw, c0, c1);
+  };
+  const auto mmg = [](const u32x4& g0, const u32x4& g1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
+    if constexpr (FL) asm volatile("" ::"v"(g0), "v"(g1), "v"(kg_bits(bw)));
+    else kg_mfma_x3_pre(pd_ung(g0), pd_ung(g1), bw, c0, c1);
+  };
+  const auto mmf = [](const f32x4& a0, const f32x4& a1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
+    kg_mfma_x3_pre(kg_pack(a0), kg_pack(a1), bw, c0, c1);
   };
   constexpr int NI = TM / 128;          // 16-position key / location tiles per wave
   constexpr int NWE = TM / 64;          // waves holding one energy per lane in the softmax
   constexpr int CWN = TM == PD_TMAX ? 288 : 544;  // cumulative-alignment floats (zero padded)
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* const sW1h = sm;              // [64 kg][64 lanes] f32x4: W1 recurrent rows of this tile
+  float* const sW1h = sm;              // [64 kg][64 lanes] kg_pk: W1 recurrent rows of this tile
   float* const sW2h = sm + 16384;      // same for W2
   float* const red = sm + 32768;       // [8][512] partial tiles / stage scratch (tail jobs: during waits)
   float* const G = red + 4096;         // [32][16] spare tile
@@ -377,16 +422,16 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   // ---------------- prologue: resident weights and per-row constants ----------------
   const int tid = tid_, lane = tid & 63, w = tid >> 6;
   const int em = (tid >> 2) & 31, eu = tid & 3;  // LSTM epilogue thread (tid < 128) -> row, unit
-  // every WF weight below comes pre-scaled by KG_SB (split fp16x3 range, common.h); the gate and
-  // projection sums are unscaled by KG_UNSCALE where they are consumed
-  f32x4 w1p[2], w2i[8];                          // chain: L1 prenet rows, L2 input rows (8 waves)
+  // every WF weight below comes pre-scaled by KG_SB and pre-split (kg_pk, common.h: split once at
+  // finalize); the gate and projection sums are unscaled by KG_UNSCALE where they are consumed
+  kg_pk w1p[2], w2i[8];                          // chain: L1 prenet rows, L2 input rows (8 waves)
   {
-    const f32x4* L1 = reinterpret_cast<const f32x4*>(a.l1_w + (long)g * K1S * 16);
-    const f32x4* L2 = reinterpret_cast<const f32x4*>(a.l2_w + (long)g * PD_H * 16);
+    const float* L1 = a.l1_w + (long)g * K1S * 16;
+    const float* L2 = a.l2_w + (long)g * PD_H * 16;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) w1p[i] = L1[(2 * w + i) * 64 + lane];  // pre-scaled (common.h)
+    for (int i = 0; i < 2; ++i) w1p[i] = kg_ld(L1, (2 * w + i) * 64 + lane);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) w2i[i] = L2[(8 * w + i) * 64 + lane];
+    for (int i = 0; i < 8; ++i) w2i[i] = kg_ld(L2, (8 * w + i) * 64 + lane);
     const f32x4* L1h = reinterpret_cast<const f32x4*>(a.l1_wh + (long)g * PD_H * 16);
     const f32x4* L2h = reinterpret_cast<const f32x4*>(a.l2_wh + (long)g * PD_H * 16);
     f32x4* d1 = reinterpret_cast<f32x4*>(sW1h);
@@ -397,25 +442,23 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     }
   }
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 wpc = zero4;
-  if (isproj && w < 4 && !isq) {
-    const f32x4* PW = reinterpret_cast<const f32x4*>(a.proj_w + (long)pn * (PD_H + PD_E2) * 16);
-    wpc = PW[(PD_H / 16 + 4 * pks + w) * 64 + lane];
-  }
+  const kg_pk zeropk = kg_pk_bits(u32x4{0u, 0u, 0u, 0u});
+  kg_pk wpc = zeropk;
+  if (isproj && w < 4 && !isq) wpc = kg_ld(a.proj_w + (long)pn * (PD_H + PD_E2) * 16, (PD_H / 16 + 4 * pks + w) * 64 + lane);
   // projection h2 rows of this split, k-group 8 pks + w (read in the C tail; L2-resident)
-  const f32x4* const WPH = reinterpret_cast<const f32x4*>(a.proj_w + (long)pn * (PD_H + PD_E2) * 16) + (8 * pks) * 64;
-  f32x4 w1c[4];  // L1 context rows, k-groups 16 + 4w + i of the tile
+  const float* const WPH = a.proj_w + (long)pn * (PD_H + PD_E2) * 16 + (8 * pks) * 64 * 4;
+  kg_pk w1c[4];  // L1 context rows, k-groups 16 + 4w + i of the tile
   {
-    const f32x4* W1C = reinterpret_cast<const f32x4*>(a.l1_w + (long)g * K1S * 16) + (PD_P / 16 + 4 * w) * 64;
+    const float* W1C = a.l1_w + (long)g * K1S * 16 + (PD_P / 16 + 4 * w) * 64 * 4;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w1c[i] = W1C[i * 64 + lane];
+    for (int i = 0; i < 4; ++i) w1c[i] = kg_ld(W1C, i * 64 + lane);
   }
-  f32x4 w1e = zero4, wdf = zero4;  // EMT: L1 emotion-block rows (k-group 48 + w); dense fragment (q blocks)
+  kg_pk w1e = zeropk, wdf = zeropk;  // EMT: L1 emotion-block rows (k-group 48 + w); dense fragment (q blocks)
   if constexpr (EMT) {
     if (w < a.e_XW / 16)  // the block's k-groups ('style_tokens': 4 of the 8 waves)
-      w1e = reinterpret_cast<const f32x4*>(a.l1_w + (long)g * K1S * 16)[((PD_P + PD_E2) / 16 + w) * 64 + lane];
+      w1e = kg_ld(a.l1_w + (long)g * K1S * 16, ((PD_P + PD_E2) / 16 + w) * 64 + lane);
     if (a.e_dense && isq && w < a.e_KC / 128)
-      wdf = reinterpret_cast<const f32x4*>(a.e_wd + (long)(pn - PD_NTILE) * a.e_KC * 16)[(pks * (a.e_KC / 128) + w) * 64 + lane];
+      wdf = kg_ld(a.e_wd + (long)(pn - PD_NTILE) * a.e_KC * 16, (pks * (a.e_KC / 128) + w) * 64 + lane);
   }
   // location-conv WF fragments of this slice in LDS (2 KB after si: the same for every wave)
   f32x4* const swl = reinterpret_cast<f32x4*>(si + 16);
@@ -460,7 +503,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   f32x4 accC0 = zero4, accC1 = zero4;  // L1 context rows of the next step (context(-1) = 0)
   if constexpr (EMT) {  // the emotion block of step 0 (zero_state: refnet_spk alone), host-written at parity 1
     const float* XE = a.EMTx + 32 * PD_EQ;
-    mm(pd_ld4(XE, (w * 2) * 64 + lane), pd_ld4(XE, (w * 2 + 1) * 64 + lane), w1e, accC0, accC1);
+    mmf(pd_ld4f(XE, (w * 2) * 64 + lane), pd_ld4f(XE, (w * 2 + 1) * 64 + lane), w1e, accC0, accC1);
   }
   f32x4 q1a = zero4, q1b = zero4, q2a = zero4, q2b = zero4;  // this wave's Q partials of RG1, RG2
   const long BP = (long)a.B * PD_P;
@@ -514,7 +557,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       for (int ww = 0; ww < 8; ++ww) v += red[ww * 32 + tid];
       const int n = 32 * j + tid;
       const float out = rowv ? (fmaxf(v + b2p, 0.f) / 0.5f) * red[3072 + tid] : 0.f;
-      pd_put(a.PREg + par * 32 * PD_P + af_idx(b, n), tag, out);
+      pd_putw(a.PREg + par * 32 * PD_P + af_idx(b, n), tag, pd_split1(out));
     }
   };
 
@@ -528,15 +571,17 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   // took in stage B; RG2 in the A window: h2 of step t-1, which every context, projection partial
   // and prenet granule of t-1 -- taken before stage A -- was computed from).
   auto rec_half = [&](int ph, const float* X, unsigned tb, const float* Wl, int h, f32x4& Qa, f32x4& Qb, int w,
-                      int lane, bool check) {
-    const f32x4* Wv = reinterpret_cast<const f32x4*>(Wl);
-    f32x4 xv[8];
+                      int lane, bool check, bool pin) {
+    u32x4 xv[8];
     const auto ix = [&](int i) { return ((8 * w + 4 * h + (i >> 1)) * 2 + (i & 1)) * 64 + lane; };
     if (check) {
       if (!pd_take4<8>(a, ph, X, ix, tb, xv, [] { return true; })) si[8] = 1;
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) xv[i] = pd_ld4(X, ix(i));
+      // pin: all 8 loads in flight before the first product.  With no conversions left to overlap, the
+      // scheduler otherwise saves registers by loading one k-group at a time: 4 exposed round trips.
+      if (pin) __builtin_amdgcn_sched_barrier(0);
     }
     if (h == 0) {
       Qa = a.zo * Qa;
@@ -545,7 +590,8 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int sg = 8 * w + 4 * h + i;
-      mm(xv[2 * i], xv[2 * i + 1], Wv[sg * 64 + lane], Qa, Qb);
+      if (!PD_TAG_H1 && ph == PD_F_H1) mmo(xv[2 * i], xv[2 * i + 1], kg_ld(Wl, sg * 64 + lane), Qa, Qb);
+      else mm(xv[2 * i], xv[2 * i + 1], kg_ld(Wl, sg * 64 + lane), Qa, Qb);
     }
   };
   __syncthreads();
@@ -581,7 +627,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     // prenet(t) of every row arrives as AF-ordered granules {tag = (t+1)<<1 | stop bit of the
     // producing row at t-1, value}; wave w takes k-groups 2w, 2w+1 = columns [32w, 32w+32), written
     // by the 32 work-groups of slice j = w, so the 8 waves together hear from all 256.
-    f32x4 a0[2], a1[2];
+    u32x4 a0[2], a1[2];  // the granules' payloads: pre-split values (pd_split1)
     {
       const auto rp = __builtin_amdgcn_make_buffer_rsrc(a.PREg + p * 32 * PD_P, (short)0, 0x7fffffff, 0x00020000);
       unsigned sb[2] = {0u, 0u};  // stop bits of rows lane%16 and 16 + lane%16
@@ -595,7 +641,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
             const int fo = (((2 * w + i) * 2 + h) * 64 + lane) * 4;  // AF float index of the lane's float4
             const auto q0 = __builtin_amdgcn_raw_buffer_load_b128(rp, fo * 8, 0, 16);       // granules 0, 1
             const auto q1 = __builtin_amdgcn_raw_buffer_load_b128(rp, fo * 8 + 16, 0, 16);  // granules 2, 3
-            f32x4 v = {__uint_as_float(q0[0]), __uint_as_float(q0[2]), __uint_as_float(q1[0]), __uint_as_float(q1[2])};
+            const u32x4 v = {q0[0], q0[2], q1[0], q1[2]};
             ok = ok && (q0[1] >> 1) == tg && (q0[3] >> 1) == tg && (q1[1] >> 1) == tg && (q1[3] >> 1) == tg;
             if (h == 0) a0[i] = v;
             else a1[i] = v;
@@ -639,7 +685,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       // L1 context rows of t-1 (accumulated during the prenet hand-off) + this wave's RG1 partial
       f32x4 s0 = accC0 + a.one_m_zo * q1a, s1 = accC1 + a.one_m_zo * q1b;
 #pragma unroll
-      for (int i = 0; i < 2; ++i) mm(a0[i], a1[i], w1p[i], s0, s1);
+      for (int i = 0; i < 2; ++i) mmg(a0[i], a1[i], w1p[i], s0, s1);
       PD_STAMP(18);
       put_partials(s0, s1, red, w, lane);
       __syncthreads();
@@ -667,7 +713,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     if constexpr (PD_TAG_H1) pd_hint_rep(a, 0, tg, tid);
     else pd_publish_rep(a, 0, tg, tid);
     PD_STAMP(2);
-    if (t > 0) rec_half(PD_F_H2, a.H2x + (p ^ 1) * 32 * PD_H, tbp, sW2h, 1, q2a, q2b, w, lane, false);  // RG2(t), 2nd half
+    if (t > 0) rec_half(PD_F_H2, a.H2x + (p ^ 1) * 32 * PD_H, tbp, sW2h, 1, q2a, q2b, w, lane, false, true);  // RG2(t), 2nd half
     PD_STAMP(3);
     // ================= B: LSTM layer 2 =================
     // wave w multiplies h1 units [128w, 128w+128) = the rows of producers [32w, 32w+32)
@@ -679,11 +725,12 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       f32x4 s0 = a.one_m_zo * q2a, s1 = a.one_m_zo * q2b;  // + this wave's RG2 partial
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        f32x4 xv[8];
+        u32x4 xv[8];
         const auto ix = [&](int i) { return ((8 * w + 4 * h + (i >> 1)) * 2 + (i & 1)) * 64 + lane; };
         if constexpr (PD_TAG_H1 == 0) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) xv[i] = pd_ld4(X, ix(i));
+          __builtin_amdgcn_sched_barrier(0);  // all 8 loads in flight before the first product (see rec_half)
         } else if constexpr (PD_TAG_H1 == 1) {
           if (!pd_take4<8>(a, PD_F_H1, X, ix, tb, xv, [&] { return pd_poll_rep(a, PD_F_H1, 0, 32 * w, tg, lane); }))
             si[8] = 1;
@@ -691,7 +738,10 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
           if (!pd_take4<8>(a, PD_F_H1, X, ix, tb, xv, [] { return true; })) si[8] = 1;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) mm(xv[2 * i], xv[2 * i + 1], w2i[4 * h + i], s0, s1);
+        for (int i = 0; i < 4; ++i) {
+          if constexpr (PD_TAG_H1) mm(xv[2 * i], xv[2 * i + 1], w2i[4 * h + i], s0, s1);
+          else mmo(xv[2 * i], xv[2 * i + 1], w2i[4 * h + i], s0, s1);
+        }
       }
       PD_STAMP(16);
       put_partials(s0, s1, red, w, lane);
@@ -726,7 +776,8 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) kv[i] = K[(w + 8 * i) * 4 + (lane >> 4)];
     }
-    rec_half(PD_F_H1, a.H1x + p * 32 * PD_H, tb, sW1h, 0, q1a, q1b, w, lane, false);  // RG1(t+1) from h1_new(t), 1st half
+    // (not pinned: wq and kv are live here, and 8 more float4s in flight spill 24 registers in the loop)
+    rec_half(PD_F_H1, a.H1x + p * 32 * PD_H, tb, sW1h, 0, q1a, q1b, w, lane, false, false);  // RG1(t+1) from h1_new(t), 1st half
     PD_STAMP(6);
     // ================= C: query slice + partial energies (attention.py:37-69, 186-201) =================
     // wave w: h2 units [128w, 128w+128) of row b (producers [32w, 32w+32)), tagged loads
@@ -736,12 +787,15 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       const float* X = a.H2x + p * 32 * PD_H;
       // wave w reads exactly the h2 units [128w, 128w+128) its own lanes multiply: wave-local
       // exchange (LDS ops of one wave complete in order), one block barrier for the 8 wave partials
-      float hv[2];
-      if (!pd_take1<2>(a, PD_F_H2, X, [&](int i) { return af_idx(b, 128 * w + 64 * i + lane); }, tb, hv,
+      // (the 8-byte granule af_idx >> 1 of the exchange form holds the unit's hi and lo halves and its
+      // own tag; the query takes hi + lo, the value to <= 2^-22 relative)
+      u32x2 hg[2];
+      if (!pd_takev<2>(a, PD_F_H2, X, [&](int i) { return af_idx(b, 128 * w + 64 * i + lane) >> 1; }, tb, hg,
                        [&] { return pd_poll_rep(a, PD_F_H2, 1, 32 * w, tg, lane); }))
         si[8] = 1;
-      red[128 * w + lane] = hv[0];
-      red[128 * w + 64 + lane] = hv[1];
+      // af_idx & 1 = (unit >> 2) & 1 = (lane >> 2) & 1 for both units
+      red[128 * w + lane] = FL ? __uint_as_float(hg[0][0]) : pd_val(hg[0], (lane >> 2) & 1);
+      red[128 * w + 64 + lane] = FL ? __uint_as_float(hg[1][0]) : pd_val(hg[1], (lane >> 2) & 1);
       __builtin_amdgcn_wave_barrier();
       {
         const int seg = tid >> 4;
@@ -791,11 +845,12 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     if (isproj) {  // projection partial, h2_new rows of this split (Architecture_wrappers.py:243-247)
       const float* X = a.H2x + p * 32 * PD_H;
       const int sg = 8 * pks + w;  // h2 units [128 pks + 16w, +16): producers [32 pks, 32 pks + 32)
-      f32x4 s0 = zero4, s1 = zero4, xv[2];
+      f32x4 s0 = zero4, s1 = zero4;
+      u32x4 xv[2];
       if (!pd_take4<2>(a, PD_F_H2, X, [&](int i) { return (sg * 2 + i) * 64 + lane; }, tb, xv,
                        [&] { return pd_poll_rep(a, PD_F_H2, 1, 32 * pks, tg, lane); }))
         si[8] = 1;
-      mm(xv[0], xv[1], WPH[w * 64 + lane], s0, s1);
+      mm(xv[0], xv[1], kg_ld(WPH, w * 64 + lane), s0, s1);
       reduce_waves_32x16<8>(s0, s1, red, G, w, lane, tid);
       if (isq) {  // emotion query: h2 rows are all of it -> granules for the emotion work-groups
         const int m = tid >> 4, col = tid & 15;
@@ -906,11 +961,15 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
         float s = 0.f;
 #pragma unroll
         for (int ts = 0; ts < 8; ++ts) s += red[ts * 64 + tid];
-        pd_st(a.CTXx + p * 32 * PD_E2 + af_idx(b, 64 * j + tid), pd_tag(s, tb));
+        // channels tid, tid+4, tid+8, tid+12 of a 16-channel k-group are one AF float4: the lanes with
+        // (tid >> 2) & 3 == 0 gather it and store it in exchange form (16 stores of 16 bytes)
+        const int src = tid & ~12;
+        const f32x4 v = {__shfl(s, src), __shfl(s, src + 4), __shfl(s, src + 8), __shfl(s, src + 12)};
+        if ((tid & 12) == 0) pd_st_x4(a.CTXx + p * 32 * PD_E2, af_idx(b, 64 * j + tid) >> 2, v, tb);
       }
       if (tid == 64 && j == 0) pd_st(a.SSx + p * 32 + b, pd_tag(sc[2], tb));
     } else {
-      if (tid < 64) pd_st(a.CTXx + p * 32 * PD_E2 + af_idx(b, 64 * j + tid), pd_tag(0.f, tb));
+      if (tid < 64 && (tid & 12) == 0) pd_st_x4(a.CTXx + p * 32 * PD_E2, af_idx(b, 64 * j + tid) >> 2, zero4, tb);
       if (tid == 64 && j == 0) pd_st(a.SSx + p * 32 + b, pd_tag(0.f, tb));
     }
     if constexpr (EMT) {
@@ -918,7 +977,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     }
     pd_hint(a, PD_F_CTX, tg, tid);
     PD_STAMP(10);
-    rec_half(PD_F_H1, a.H1x + p * 32 * PD_H, tb, sW1h, 1, q1a, q1b, w, lane, false);  // RG1(t+1), 2nd half
+    rec_half(PD_F_H1, a.H1x + p * 32 * PD_H, tb, sW1h, 1, q1a, q1b, w, lane, false, true);  // RG1(t+1), 2nd half
     // location features of step t+1: im2col(cum) · (W_conv·W_loc) on MFMA (attention.py:59-62)
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -1064,7 +1123,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
           const float* X = a.CMBx + (long)p * 32 * a.e_KC;
           const int sg = pks * nkg + w;
           f32x4 s0 = zero4, s1 = zero4;
-          mm(pd_ld4(X, (sg * 2) * 64 + lane), pd_ld4(X, (sg * 2 + 1) * 64 + lane), wdf, s0, s1);
+          mmf(pd_ld4f(X, (sg * 2) * 64 + lane), pd_ld4f(X, (sg * 2 + 1) * 64 + lane), wdf, s0, s1);
           put_partials(s0, s1, red, w, lane);
         }
         __syncthreads();
@@ -1083,7 +1142,8 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       if (w < 4) {  // context channels [64 pks + 16w, +16): slice j = pks, producers [32 pks, 32 pks + 32)
         const float* X = a.CTXx + p * 32 * PD_E2;
         const int sg = 4 * pks + w;
-        f32x4 s0 = zero4, s1 = zero4, xv[2];
+        f32x4 s0 = zero4, s1 = zero4;
+        u32x4 xv[2];
         if (!pd_take4<2>(a, PD_F_CTX, X, [&](int i) { return (sg * 2 + i) * 64 + lane; }, tb, xv,
                          [&] { return pd_poll(a, PD_F_CTX, 32 * pks, 1, 32, tg, 0, lane); }))
           si[8] = 1;
@@ -1100,7 +1160,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       PD_STAMP(12);
     }
     // ================= F: frame / stop (modules.py:392-448), prenet of step t+1 =================
-    rec_half(PD_F_H2, a.H2x + p * 32 * PD_H, tb, sW2h, 0, q2a, q2b, w, lane, true);  // RG2(t+1) from h2_new(t), 1st half
+    rec_half(PD_F_H2, a.H2x + p * 32 * PD_H, tb, sW2h, 0, q2a, q2b, w, lane, true, false);  // RG2(t+1) from h2_new(t), 1st half
     PD_STAMP(13);
     int stopbit = 0;
     if (tid == 0) si[5] = 1;
@@ -1182,7 +1242,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       const float* XC = a.CTXx + p * 32 * PD_E2;
       accC0 = zero4;
       accC1 = zero4;
-      f32x4 xv[8];  // wave w: channels [64w, 64w + 64) = slice j = w, producers [32w, 32w + 32)
+      u32x4 xv[8];  // wave w: channels [64w, 64w + 64) = slice j = w, producers [32w, 32w + 32)
       if (!pd_take4<8>(a, PD_F_CTX, XC, [&](int i) { return ((4 * w + (i >> 1)) * 2 + (i & 1)) * 64 + lane; }, tb, xv,
                        [&] {
                          if constexpr (!EMT) {  // diagnostic: when wave w's optimistic context load missed
@@ -1205,7 +1265,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       if (!pd_block_wait(si + 6, [&] { return pd_poll_rep(a, PD_F_EMT, 2, PD_EG0, tg, lane, 16); })) return;
       PD_STAMP(29);
       const float* XE = a.EMTx + p * 32 * PD_EQ;
-      mm(pd_ld4(XE, (w * 2) * 64 + lane), pd_ld4(XE, (w * 2 + 1) * 64 + lane), w1e, accC0, accC1);
+      mmf(pd_ld4f(XE, (w * 2) * 64 + lane), pd_ld4f(XE, (w * 2 + 1) * 64 + lane), w1e, accC0, accC1);
     }
     PD_STAMP(15);
   }

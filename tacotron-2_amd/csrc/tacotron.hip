@@ -1423,8 +1423,18 @@ static void upload(DevBuf& d, const std::vector<float>& h) {
   TT2_HIP(hipMemcpy(d.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 static void upload(DevBuf& d, const HostTensor& t) { upload(d, t.data); }
-static void upload_scaled(DevBuf& d, std::vector<float> h, float scale) {
+// In place: every float4 of x (n % 4 == 0) -> its pre-split operand kg_pk (common.h), the same 16 bytes.
+static void kg_pack_host(float* x, size_t n) {
+  for (size_t i = 0; i < n; i += 4) {
+    const kg_pk p = kg_pack(f32x4{x[i], x[i + 1], x[i + 2], x[i + 3]});
+    std::memcpy(x + i, &p, sizeof(p));
+  }
+}
+// The persistent decoder's resident WF weights: pre-scaled and split once here, so no step re-splits them.
+static void upload_split(DevBuf& d, std::vector<float> h, float scale) {
+  TT2_CHECK(h.size() % 4 == 0, TT2_ERR_INVALID_ARG, "upload_split: not a whole number of float4s");
   for (float& x : h) x *= scale;  // exact: power of two
+  kg_pack_host(h.data(), h.size());
   upload(d, h);
 }
 static float absmax(const std::vector<float>& v) {
@@ -1643,8 +1653,8 @@ static void finalize(tt2_ctx* c) {
       upload(l == 0 ? c->l1_wh : c->l2_wh, wr);
       if (H % 16 == 0) {  // persistent decoder tiles (pd_fits also requires H == PD_H)
         const auto pc = pd_lstm_cols(H);
-        upload_scaled(l == 0 ? c->pd_l1_w : c->pd_l2_w, pack_wf(k.data.data(), Kc, N, pc, Kc), KG_SB);
-        upload_scaled(l == 0 ? c->pd_l1_wh : c->pd_l2_wh, pack_wf(k.data.data() + (size_t)Kh0 * N, H, N, pc, H), KG_SB);
+        upload_split(l == 0 ? c->pd_l1_w : c->pd_l2_w, pack_wf(k.data.data(), Kc, N, pc, Kc), KG_SB);
+        upload_split(l == 0 ? c->pd_l1_wh : c->pd_l2_wh, pack_wf(k.data.data() + (size_t)Kh0 * N, H, N, pc, H), KG_SB);
       }
     }
     upload(l == 0 ? c->l1_b : c->l2_b, bt);
@@ -1749,7 +1759,7 @@ static void finalize(tt2_ctx* c) {
         }
         const auto pwx = pack_wf(Wx.data(), c->Kp, NX, colx, c->Kp);
         c->kg_wmax_dec = std::max(c->kg_wmax_dec, absmax(pwx));
-        upload_scaled(c->pd_proj_w, pwx, KG_SB);
+        upload_split(c->pd_proj_w, pwx, KG_SB);
         if (c->emt.attn == EMT_MULTIHEAD) {  // the attn_emt dense as WF tiles ('style_tokens' has none)
           const int KC = c->emt.heads * c->emt.Dv;
           const auto& kd = need(wm, P + "decoder/attn_emt/dense/kernel", {KC, EMT_OUT});
@@ -1757,10 +1767,10 @@ static void finalize(tt2_ctx* c) {
           for (int j = 0; j < EMT_OUT; ++j) ocols.push_back(j);
           const auto pwd = pack_wf(kd.data.data(), KC, EMT_OUT, ocols, KC);
           c->kg_wmax_dec = std::max(c->kg_wmax_dec, absmax(pwd));
-          upload_scaled(c->pd_e_wd, pwd, KG_SB);
+          upload_split(c->pd_e_wd, pwd, KG_SB);
         }
       } else {
-        upload_scaled(c->pd_proj_w, pw, KG_SB);
+        upload_split(c->pd_proj_w, pw, KG_SB);
       }
     }
     std::vector<float> ws((size_t)c->SW * NPF, 0.f);                // context_style rows
@@ -3195,6 +3205,15 @@ tt2_status tt2_debug_pd_stamps(tt2_ctx* c, long long* out8192) {
     TT2_CHECK(g_pd_stamps_dev, TT2_ERR_STATE, "no persistent decode ran with TT2_STAMP_STEP set");
     TT2_HIP(hipDeviceSynchronize());
     TT2_HIP(hipMemcpy(out8192, g_pd_stamps_dev, PD_NB * 32 * sizeof(long long), hipMemcpyDeviceToHost));
+  });
+}
+
+tt2_status tt2_debug_kg_pack(const float* x, long long n, uint16_t* out) {
+  return guard([&] {
+    TT2_CHECK(x && out && n >= 0 && n % 4 == 0, TT2_ERR_INVALID_ARG, "tt2_debug_kg_pack: null argument or n % 4 != 0");
+    std::vector<float> v(x, x + n);
+    kg_pack_host(v.data(), v.size());
+    std::memcpy(out, v.data(), sizeof(float) * v.size());
   });
 }
 
