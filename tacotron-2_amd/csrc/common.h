@@ -233,6 +233,38 @@ __device__ __forceinline__ void kg_mfma_x3_pre(const kg_pk& a0, const kg_pk& a1,
   c0 = __builtin_amdgcn_mfma_f32_16x16x16f16(a0.h, bw.h, c0, 0, 0, 0);
   c1 = __builtin_amdgcn_mfma_f32_16x16x16f16(a1.h, bw.h, c1, 0, 0, 0);
 }
+// Pair form: two k-groups sg, sg+1 as ONE v_mfma_f32_16x16x32_f16 operand per term.  Lane l's 8 halves
+// are k = 16sg + 4e + (l>>4) (e < 4), then the same of sg+1 -- on both operands, so the (l>>4, element)
+// -> k map stays consistent and the product is the sum over the 32 k's whatever order the hardware
+// gives them.  Three MFMAs per row half instead of six, the same lo·hi, hi·lo, hi·hi order; the fp32
+// sums of two k-groups' products join in a different order, so results move by rounding only.
+typedef _Float16 kg_f16x8 __attribute__((ext_vector_type(8)));
+struct alignas(16) kg_pk2 {
+  kg_f16x8 h, l;
+};
+__device__ __forceinline__ kg_pk2 kg_pair(const kg_pk& p, const kg_pk& q) {
+  kg_pk2 r;
+  r.h = __builtin_shufflevector(p.h, q.h, 0, 1, 2, 3, 4, 5, 6, 7);
+  r.l = __builtin_shufflevector(p.l, q.l, 0, 1, 2, 3, 4, 5, 6, 7);
+  return r;
+}
+// one stored pair: the hi plane [64 lanes] x 16 bytes, then the lo plane (two conflict-free 1 KiB reads)
+__device__ __forceinline__ kg_pk2 kg_ld2(const float* base, int pr, int lane) {
+  const u32x4* v = reinterpret_cast<const u32x4*>(base);
+  kg_pk2 r;
+  r.h = __builtin_bit_cast(kg_f16x8, v[(pr * 2 + 0) * 64 + lane]);
+  r.l = __builtin_bit_cast(kg_f16x8, v[(pr * 2 + 1) * 64 + lane]);
+  return r;
+}
+__device__ __forceinline__ void kg_mfma_x3_pre2(const kg_pk2& a0, const kg_pk2& a1, const kg_pk2& bw, f32x4& c0,
+                                                f32x4& c1) {
+  c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0.l, bw.h, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1.l, bw.h, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0.h, bw.l, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1.h, bw.l, c1, 0, 0, 0);
+  c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0.h, bw.h, c0, 0, 0, 0);
+  c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1.h, bw.h, c1, 0, 0, 0);
+}
 // bw is the pre-scaled (x KG_SB) weight fragment; c0/c1 accumulate A·B·2^10.
 __device__ __forceinline__ void kg_mfma_x3(const f32x4& a0, const f32x4& a1, const f32x4& bw, f32x4& c0,
                                            f32x4& c1) {

@@ -90,6 +90,17 @@ __device__ __forceinline__ bool pd_spin(const PdArgs& a, int ph, int lane, F con
   }
 }
 
+// wave-uniform minimum of 64 lanes (as wave_max_dpp, common.h)
+__device__ __forceinline__ int pd_wave_min(int v) {
+  v = min(v, dpp_i<DPP_XOR1>(v));
+  v = min(v, dpp_i<DPP_XOR2>(v));
+  v = min(v, dpp_i<DPP_HALF_MIRROR>(v));
+  v = min(v, dpp_i<DPP_MIRROR>(v));
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false));  // row_bcast:15
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false));  // row_bcast:31
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
 __device__ __forceinline__ unsigned pd_flag(const unsigned* f) {
   return __hip_atomic_load((pd_gu32*)const_cast<unsigned*>(f), PD_RLX);
 }
@@ -370,27 +381,40 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   static_assert(!FL || (!EMT && TM == PD_TMAX), "floor instance: the Tacotron decoder only");
   // acc(rows 0..15 | 16..31) += A(k-group) · W(k-group, 16 columns), split fp16x3 from pre-split
   // operands (common.h), or (FL) the operands sunk as loaded.  mm: activations in exchange form;
-  // mmg: as the payloads of 4 prenet granules; mmf: as fp32 (the EMT-only exchanges).
+  // mmf: as fp32 (the EMT-only exchanges).  Both for the single-k-group products.
   const auto mm = [](const u32x4& x0, const u32x4& x1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
     if constexpr (FL) asm volatile("" ::"v"(x0), "v"(x1), "v"(kg_bits(bw)));
     else kg_mfma_x3_pre(pd_unx(x0), pd_unx(x1), bw, c0, c1);
   };
-  const auto mmo = [](const u32x4& x0, const u32x4& x1, const kg_pk& bw, f32x4& c0, f32x4& c1) {  // untagged h1
-    if constexpr (FL) asm volatile("" ::"v"(x0), "v"(x1), "v"(kg_bits(bw)));
-    else kg_mfma_x3_pre(kg_pk_bits(x0), kg_pk_bits(x1), bw, c0, c1);
-  };
-  const auto mmg = [](const u32x4& g0, const u32x4& g1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
-    if constexpr (FL) asm volatile("" ::"v"(g0), "v"(g1), "v"(kg_bits(bw)));
-    else kg_mfma_x3_pre(pd_ung(g0), pd_ung(g1), bw, c0, c1);
-  };
   const auto mmf = [](const f32x4& a0, const f32x4& a1, const kg_pk& bw, f32x4& c0, f32x4& c1) {
     kg_mfma_x3_pre(kg_pack(a0), kg_pack(a1), bw, c0, c1);
+  };
+  // Pair forms (common.h, kg_mfma_x3_pre2): k-groups sg (p0 | p1 = rows 0..15 | 16..31) and sg + 1 (q0 | q1)
+  // against one paired weight fragment -- wherever a wave multiplies an even run of k-groups.
+  const auto sink2 = [](const u32x4& p0, const u32x4& p1, const u32x4& q0, const u32x4& q1, const kg_pk2& bw) {
+    asm volatile("" ::"v"(p0), "v"(p1), "v"(q0), "v"(q1), "v"(__builtin_bit_cast(u32x4, bw.h)),
+                 "v"(__builtin_bit_cast(u32x4, bw.l)));
+  };
+  const auto mm2 = [&](const u32x4& p0, const u32x4& p1, const u32x4& q0, const u32x4& q1, const kg_pk2& bw, f32x4& c0,
+                       f32x4& c1) {
+    if constexpr (FL) sink2(p0, p1, q0, q1, bw);
+    else kg_mfma_x3_pre2(kg_pair(pd_unx(p0), pd_unx(q0)), kg_pair(pd_unx(p1), pd_unx(q1)), bw, c0, c1);
+  };
+  const auto mmo2 = [&](const u32x4& p0, const u32x4& p1, const u32x4& q0, const u32x4& q1, const kg_pk2& bw, f32x4& c0,
+                        f32x4& c1) {  // untagged h1
+    if constexpr (FL) sink2(p0, p1, q0, q1, bw);
+    else kg_mfma_x3_pre2(kg_pair(kg_pk_bits(p0), kg_pk_bits(q0)), kg_pair(kg_pk_bits(p1), kg_pk_bits(q1)), bw, c0, c1);
+  };
+  const auto mmg2 = [&](const u32x4& p0, const u32x4& p1, const u32x4& q0, const u32x4& q1, const kg_pk2& bw, f32x4& c0,
+                        f32x4& c1) {  // the payloads of 4 prenet granules each
+    if constexpr (FL) sink2(p0, p1, q0, q1, bw);
+    else kg_mfma_x3_pre2(kg_pair(pd_ung(p0), pd_ung(q0)), kg_pair(pd_ung(p1), pd_ung(q1)), bw, c0, c1);
   };
   constexpr int NI = TM / 128;          // 16-position key / location tiles per wave
   constexpr int NWE = TM / 64;          // waves holding one energy per lane in the softmax
   constexpr int CWN = TM == PD_TMAX ? 288 : 544;  // cumulative-alignment floats (zero padded)
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* const sW1h = sm;              // [64 kg][64 lanes] kg_pk: W1 recurrent rows of this tile
+  float* const sW1h = sm;              // [32 kg pairs][hi | lo][64 lanes] 16 B (kg_ld2): W1 recurrent rows of this tile
   float* const sW2h = sm + 16384;      // same for W2
   float* const red = sm + 32768;       // [8][512] partial tiles / stage scratch (tail jobs: during waits)
   float* const G = red + 4096;         // [32][16] spare tile
@@ -424,21 +448,26 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   const int em = (tid >> 2) & 31, eu = tid & 3;  // LSTM epilogue thread (tid < 128) -> row, unit
   // every WF weight below comes pre-scaled by KG_SB and pre-split (kg_pk, common.h: split once at
   // finalize); the gate and projection sums are unscaled by KG_UNSCALE where they are consumed
-  kg_pk w1p[2], w2i[8];                          // chain: L1 prenet rows, L2 input rows (8 waves)
+  // k-groups are paired here, once (kg_pair / the kg_ld2 planes in LDS): the stored copies keep kg_pack's order
+  kg_pk2 w1p, w2i[4];                            // chain: L1 prenet rows, L2 input rows (8 waves)
   {
     const float* L1 = a.l1_w + (long)g * K1S * 16;
     const float* L2 = a.l2_w + (long)g * PD_H * 16;
+    w1p = kg_pair(kg_ld(L1, (2 * w) * 64 + lane), kg_ld(L1, (2 * w + 1) * 64 + lane));
 #pragma unroll
-    for (int i = 0; i < 2; ++i) w1p[i] = kg_ld(L1, (2 * w + i) * 64 + lane);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w2i[i] = kg_ld(L2, (8 * w + i) * 64 + lane);
-    const f32x4* L1h = reinterpret_cast<const f32x4*>(a.l1_wh + (long)g * PD_H * 16);
-    const f32x4* L2h = reinterpret_cast<const f32x4*>(a.l2_wh + (long)g * PD_H * 16);
-    f32x4* d1 = reinterpret_cast<f32x4*>(sW1h);
-    f32x4* d2 = reinterpret_cast<f32x4*>(sW2h);
-    for (int e = tid; e < PD_H * 4; e += PD_NT) {
-      d1[e] = L1h[e];
-      d2[e] = L2h[e];
+    for (int i = 0; i < 4; ++i) w2i[i] = kg_pair(kg_ld(L2, (8 * w + 2 * i) * 64 + lane), kg_ld(L2, (8 * w + 2 * i + 1) * 64 + lane));
+    const u32x4* L1h = reinterpret_cast<const u32x4*>(a.l1_wh + (long)g * PD_H * 16);
+    const u32x4* L2h = reinterpret_cast<const u32x4*>(a.l2_wh + (long)g * PD_H * 16);
+    u32x2* d1 = reinterpret_cast<u32x2*>(sW1h);
+    u32x2* d2 = reinterpret_cast<u32x2*>(sW2h);
+    for (int e = tid; e < PD_H * 4; e += PD_NT) {  // k-group e / 64, lane e % 64: {H01, H23, L01, L23}
+      const int sg = e >> 6, l = e & 63;
+      const int dh = (((sg >> 1) * 2 + 0) * 64 + l) * 2 + (sg & 1), dl = (((sg >> 1) * 2 + 1) * 64 + l) * 2 + (sg & 1);
+      const u32x4 v1 = L1h[e], v2 = L2h[e];
+      d1[dh] = u32x2{v1[0], v1[1]};
+      d1[dl] = u32x2{v1[2], v1[3]};
+      d2[dh] = u32x2{v2[0], v2[1]};
+      d2[dl] = u32x2{v2[2], v2[3]};
     }
   }
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -447,11 +476,11 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
   if (isproj && w < 4 && !isq) wpc = kg_ld(a.proj_w + (long)pn * (PD_H + PD_E2) * 16, (PD_H / 16 + 4 * pks + w) * 64 + lane);
   // projection h2 rows of this split, k-group 8 pks + w (read in the C tail; L2-resident)
   const float* const WPH = a.proj_w + (long)pn * (PD_H + PD_E2) * 16 + (8 * pks) * 64 * 4;
-  kg_pk w1c[4];  // L1 context rows, k-groups 16 + 4w + i of the tile
+  kg_pk2 w1c[2];  // L1 context rows, k-groups 16 + 4w + 2i, +1 of the tile
   {
     const float* W1C = a.l1_w + (long)g * K1S * 16 + (PD_P / 16 + 4 * w) * 64 * 4;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w1c[i] = kg_ld(W1C, i * 64 + lane);
+    for (int i = 0; i < 2; ++i) w1c[i] = kg_pair(kg_ld(W1C, (2 * i) * 64 + lane), kg_ld(W1C, (2 * i + 1) * 64 + lane));
   }
   kg_pk w1e = zeropk, wdf = zeropk;  // EMT: L1 emotion-block rows (k-group 48 + w); dense fragment (q blocks)
   if constexpr (EMT) {
@@ -588,10 +617,10 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       Qb = a.zo * Qb;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int sg = 8 * w + 4 * h + i;
-      if (!PD_TAG_H1 && ph == PD_F_H1) mmo(xv[2 * i], xv[2 * i + 1], kg_ld(Wl, sg * 64 + lane), Qa, Qb);
-      else mm(xv[2 * i], xv[2 * i + 1], kg_ld(Wl, sg * 64 + lane), Qa, Qb);
+    for (int i = 0; i < 2; ++i) {
+      const kg_pk2 bw = kg_ld2(Wl, 4 * w + 2 * h + i, lane);  // k-groups 8w + 4h + 2i, +1
+      if (!PD_TAG_H1 && ph == PD_F_H1) mmo2(xv[4 * i], xv[4 * i + 1], xv[4 * i + 2], xv[4 * i + 3], bw, Qa, Qb);
+      else mm2(xv[4 * i], xv[4 * i + 1], xv[4 * i + 2], xv[4 * i + 3], bw, Qa, Qb);
     }
   };
   __syncthreads();
@@ -684,8 +713,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     {
       // L1 context rows of t-1 (accumulated during the prenet hand-off) + this wave's RG1 partial
       f32x4 s0 = accC0 + a.one_m_zo * q1a, s1 = accC1 + a.one_m_zo * q1b;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) mmg(a0[i], a1[i], w1p[i], s0, s1);
+      mmg2(a0[0], a1[0], a0[1], a1[1], w1p, s0, s1);
       PD_STAMP(18);
       put_partials(s0, s1, red, w, lane);
       __syncthreads();
@@ -738,9 +766,9 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
           if (!pd_take4<8>(a, PD_F_H1, X, ix, tb, xv, [] { return true; })) si[8] = 1;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if constexpr (PD_TAG_H1) mm(xv[2 * i], xv[2 * i + 1], w2i[4 * h + i], s0, s1);
-          else mmo(xv[2 * i], xv[2 * i + 1], w2i[4 * h + i], s0, s1);
+        for (int i = 0; i < 2; ++i) {
+          if constexpr (PD_TAG_H1) mm2(xv[4 * i], xv[4 * i + 1], xv[4 * i + 2], xv[4 * i + 3], w2i[2 * h + i], s0, s1);
+          else mmo2(xv[4 * i], xv[4 * i + 1], xv[4 * i + 2], xv[4 * i + 3], w2i[2 * h + i], s0, s1);
         }
       }
       PD_STAMP(16);
@@ -782,7 +810,16 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
     // ================= C: query slice + partial energies (attention.py:37-69, 186-201) =================
     // wave w: h2 units [128w, 128w+128) of row b (producers [32w, 32w+32)), tagged loads
     PD_STAMP(7);
-
+    // Projection blocks: the two h2 loads of the C tail's partial (k-group 8 pks + w: producers [32 pks,
+    // 32 pks + 32)), issued behind the query's block barrier: every wave's own h2 take has landed, and the
+    // W_q slice's registers are free.  They are in flight across the energies instead of a round trip of
+    // their own behind them.  Optimistic: the tail checks the tags.  (A padding row's work-group has no
+    // query or energies to hide them behind and takes them there.)
+    u32x4 xph[2];
+    const auto projh_ld = [&] {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) xph[i] = pd_ld4(a.H2x + p * 32 * PD_H, ((8 * pks + w) * 2 + i) * 64 + lane);
+    };
     if (rowv) {
       const float* X = a.H2x + p * 32 * PD_H;
       // wave w reads exactly the h2 units [128w, 128w+128) its own lanes multiply: wave-local
@@ -812,6 +849,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
         if (lane < 16) red[1024 + w * 16 + lane] = s;
       }
       __syncthreads();
+      if (isproj) projh_ld();
       float qk = 0.f;
 #pragma unroll
       for (int ww = 0; ww < 8; ++ww) qk += red[1024 + ww * 16 + (lane & 15)];
@@ -839,6 +877,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       for (int i = 1; i < NI; ++i) vo = (lane >> 4) == i ? vi[i] : vo;
       if (lane < 16 * NI) pd_put(E + (w + 8 * (lane >> 4)) * 16 + (lane & 15), tg, vo);
     }
+    if (tid == 0) si[5] = 1;  // stage D's take-failure flag: reset under this barrier
     __syncthreads();  // red / qv reuse below
     if (si[8]) return;
     PD_STAMP(8);
@@ -846,11 +885,13 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       const float* X = a.H2x + p * 32 * PD_H;
       const int sg = 8 * pks + w;  // h2 units [128 pks + 16w, +16): producers [32 pks, 32 pks + 32)
       f32x4 s0 = zero4, s1 = zero4;
-      u32x4 xv[2];
-      if (!pd_take4<2>(a, PD_F_H2, X, [&](int i) { return (sg * 2 + i) * 64 + lane; }, tb, xv,
+      // the early loads normally carry this step's tags; after a miss, the take as before (flag hint, retry)
+      const bool hit = rowv && __all(pd_ok4(xph[0], tb) && pd_ok4(xph[1], tb));
+      if (!hit &&
+          !pd_take4<2>(a, PD_F_H2, X, [&](int i) { return (sg * 2 + i) * 64 + lane; }, tb, xph,
                        [&] { return pd_poll_rep(a, PD_F_H2, 1, 32 * pks, tg, lane); }))
         si[8] = 1;
-      mm(xv[0], xv[1], kg_ld(WPH, w * 64 + lane), s0, s1);
+      mm(xph[0], xph[1], kg_ld(WPH, w * 64 + lane), s0, s1);
       reduce_waves_32x16<8>(s0, s1, red, G, w, lane, tid);
       if (isq) {  // emotion query: h2 rows are all of it -> granules for the emotion work-groups
         const int m = tid >> 4, col = tid & 15;
@@ -872,8 +913,6 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) vhi[i] = V[i];
       }
-      if (tid == 0) si[5] = 1;
-      __syncthreads();
       // waves 0..NWE-1 hold one energy per lane; max and sum as wave shuffles + one LDS exchange of
       // the wave results each
       float e = -INFINITY;
@@ -911,37 +950,26 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
       if (tid < TM) {
         float den = (red[8] + red[9]) + (red[10] + red[11]);
         if constexpr (NWE == 8) den += (red[12] + red[13]) + (red[14] + red[15]);
-        al[tid] = tid < T ? ex * __builtin_amdgcn_rcpf(den) : 0.f;
+        const float av = tid < T ? ex * __builtin_amdgcn_rcpf(den) : 0.f;
+        al[tid] = av;
+        // max_att = argmax (ties -> first) and Σ_{t<len} alignments, per wave from the registers that hold
+        // the alignments (DPP, no LDS round trips); one thread joins the NWE wave results below, beside the
+        // context store.  (A loop of wave 1 over al with 18 ds_bpermute shuffles stood here, between the
+        // alignments and the context partials, and all 8 waves waited for it.)
+        const float wm = wave_max_dpp(av);
+        const int wi = pd_wave_min(tid < T && av == wm ? tid : 0x7fffffff);
+        const float ws = wave_sum_dpp(tid < len ? av : 0.f);
+        if (lane == 0) {
+          G[w] = wm;
+          G[8 + w] = __int_as_float(wi);
+          G[16 + w] = ws;
+        }
       }
       __syncthreads();
       if (tid < T) {
         const float cp = cw[15 + tid];
         cw[15 + tid] = a.cumulative ? al[tid] + cp : al[tid];
         if (j == 0 && a.align) a.align[((long)b * a.max_iters + t) * T + tid] = al[tid];  // step-major
-      }
-      if (w == 1) {  // max_att = argmax (ties -> first), Σ_{t<len} alignments
-        float best = -INFINITY, ss = 0.f;
-        int bi = 0x7fffffff;
-        for (int i = lane; i < T; i += 64) {
-          if (al[i] > best) {
-            best = al[i];
-            bi = i;
-          }
-          if (i < len) ss += al[i];
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-          const float ob = __shfl_xor(best, o);
-          const int oi = __shfl_xor(bi, o);
-          if (ob > best || (ob == best && oi < bi)) {
-            best = ob;
-            bi = oi;
-          }
-          ss += __shfl_xor(ss, o);
-        }
-        if (lane == 0) {
-          si[0] = bi;
-          sc[2] = ss;
-        }
       }
       {
         const int c = tid & 63, ts = tid >> 6;
@@ -967,7 +995,21 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
         const f32x4 v = {__shfl(s, src), __shfl(s, src + 4), __shfl(s, src + 8), __shfl(s, src + 12)};
         if ((tid & 12) == 0) pd_st_x4(a.CTXx + p * 32 * PD_E2, af_idx(b, 64 * j + tid) >> 2, v, tb);
       }
-      if (tid == 64 && j == 0) pd_st(a.SSx + p * 32 + b, pd_tag(sc[2], tb));
+      if (tid == 64) {  // si[0] is read in the next step, sc[2] behind the PP take
+        float best = G[0], ss = G[16];
+        int bi = __float_as_int(G[8]);
+#pragma unroll
+        for (int ww = 1; ww < NWE; ++ww) {
+          if (G[ww] > best) {  // ascending positions: a tie keeps the first
+            best = G[ww];
+            bi = __float_as_int(G[8 + ww]);
+          }
+          ss += G[16 + ww];
+        }
+        si[0] = bi;
+        sc[2] = ss;
+        if (j == 0) pd_st(a.SSx + p * 32 + b, pd_tag(ss, tb));
+      }
     } else {
       if (tid < 64 && (tid & 12) == 0) pd_st_x4(a.CTXx + p * 32 * PD_E2, af_idx(b, 64 * j + tid) >> 2, zero4, tb);
       if (tid == 64 && j == 0) pd_st(a.SSx + p * 32 + b, pd_tag(0.f, tb));
@@ -1252,7 +1294,7 @@ __global__ __launch_bounds__(PD_NT) void k_decode_persist(PdArgs a) {
                        }))
         si[8] = 1;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) mm(xv[2 * i], xv[2 * i + 1], w1c[i], accC0, accC1);
+      for (int i = 0; i < 2; ++i) mm2(xv[4 * i], xv[4 * i + 1], xv[4 * i + 2], xv[4 * i + 3], w1c[i], accC0, accC1);
       if (w == 0) {  // Σ_{t<len} align of every row (written by the j = 0 work-groups, producers [0, 32))
         float sv[1];
         if (!pd_take1<1>(a, PD_F_CTX, a.SSx + p * 32, [&](int) { return lane & 31; }, tb, sv,
